@@ -13,6 +13,29 @@ import os
 
 import time
 
+# --dump-outputs stays well under 64 MB in all: fields larger than their
+# share of this budget are reduced to a seeded sample of their cells
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(app, out_dir, rank, n_domains):
+    """Write the temperature field every local domain holds after the last
+    timed step (what read_global hands a caller) as float32
+    <out_dir>/temp_r<rank>_d<local index>.npy. A field over its share of
+    the budget is written as the cells at fixed, seeded flat (z,y,x)
+    indices, so two runs with the same arguments dump the same cells."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    per_domain = DUMP_BUDGET_BYTES // 4 // n_domains
+    for li in range(app.dd.num_local()):
+        lo, hi = app.dd.local_rect(li)
+        arr = np.asarray(app.dd.read_global(li, lo, hi, app.h), dtype=np.float32)
+        if arr.size > per_domain:
+            idx = np.sort(np.random.default_rng(750).integers(0, arr.size, per_domain))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"temp_r{rank}_d{li}.npy"), arr)
+
 
 def weak_dims(n):
     """split factor per axis for n GPUs (largest-prime-first, smallest axis)"""
@@ -36,6 +59,14 @@ def main():
                     "(measured -7%% step time at m=2 on 1 GPU; default 1 = the "
                     "reference's per-step-exchange configuration)")
     ap.add_argument("--backend", default="native")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the resulting temperature "
+                    "field(s) as DIR/temp_r<rank>_d<domain>.npy (float32; a seeded "
+                    "sample of the cells when the field is large)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure; "
+                    "there are none yet, anything that is added to this script "
+                    "besides the timed steps belongs behind this option")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -114,6 +145,9 @@ def main():
         t = torch.tensor([xbytes], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=ctrl)
         xbytes = float(t.item())
+
+    if args.dump_outputs:
+        dump_outputs(app, args.dump_outputs, rank, n_gpus)
 
     if rank == 0:
         out = {
