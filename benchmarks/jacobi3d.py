@@ -45,6 +45,12 @@ def main():
     ap.add_argument("--period", type=int, default=-1, help="paraview dump every N iters")
     ap.add_argument("--prefix", default="jacobi3d_")
     ap.add_argument("--backend", default="native")
+    ap.add_argument("--boundary", default="periodic",
+                    choices=["periodic", "fixed", "clamp", "mirror"],
+                    help="boundary kind on all six global faces (fixed: walls held at 0.5)")
+    ap.add_argument("--queued", action="store_true",
+                    help="also time all iters enqueued behind one host sync (what bench.py "
+                    "times in graph mode) and append ms_per_step_queued")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -69,8 +75,15 @@ def main():
         size = tuple(args.size * d for d in dims)
 
     placement = PlacementStrategy.Trivial if args.trivial else PlacementStrategy.NodeAware
+    boundary = {
+        "periodic": None,
+        "fixed": {"all": (sa.Boundary.FIXED, 0.5)},
+        "clamp": {"all": sa.Boundary.CLAMP},
+        "mirror": {"all": sa.Boundary.MIRROR},
+    }[args.boundary]
     app = Jacobi3D(size, backend=args.backend, gpus=gpus, placement=placement,
-                   radius=args.radius, halo_multiplier=args.halo_multiplier)
+                   radius=args.radius, halo_multiplier=args.halo_multiplier,
+                   boundary=boundary)
     app.realize()
 
     stats = Statistics()
@@ -86,6 +99,12 @@ def main():
             app.dd.write_paraview(f"{args.prefix}iter{i + 1}_")
 
     mn, tm = stats.min(), stats.trimean()
+    # queued run: all steps enqueued, one host sync (what bench.py times in
+    # graph mode), so the figure compares with its ms_per_step
+    queued_ms = None
+    if args.queued and world == 1:
+        app.dd.backend.sync()
+        queued_ms = app.run(args.iters) / args.iters * 1e3
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -101,7 +120,10 @@ def main():
         mode = "strong" if args.strong else "weak"
         print(
             f"jacobi3d,{mode},ranks={world},gpus={n},{size[0]},{size[1]},{size[2]},"
-            f"bytes_kernel={bk},bytes_rccl={br},min={mn:.6f},trimean={tm:.6f}",
+            f"bytes_kernel={bk},bytes_rccl={br},min={mn:.6f},trimean={tm:.6f}"
+            + (f",boundary={args.boundary},bytes_boundary={app.dd.boundary_bytes}"
+               if args.boundary != "periodic" else "")
+            + (f",ms_per_step_queued={queued_ms:.4f}" if queued_ms is not None else ""),
             flush=True,
         )
 

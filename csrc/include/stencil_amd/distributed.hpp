@@ -22,9 +22,11 @@
 //     RCCL one.)
 #pragma once
 
+#include <array>
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "stencil_amd/core.hpp"
@@ -61,12 +63,26 @@ public:
   void set_radius(int64_t r) { radius_ = Radius::constant(r); }
   int64_t add_data(int64_t elemSize, const std::string &name = "");
   template <typename T> int64_t add_data(const std::string &name = "") {
-    return add_data((int64_t)sizeof(T), name);
+    const int64_t qi = add_data((int64_t)sizeof(T), name);
+    isFloat_[qi] = std::is_floating_point<T>::value;
+    isSigned_[qi] = std::is_signed<T>::value;
+    return qi;
   }
   void set_gpus(const std::vector<int> &gpus) { gpus_ = gpus; }
   void set_placement(PlacementStrategy s) { strategy_ = s; }
   // partition quantities into independently exchangeable groups
   void set_exchange_groups(const std::vector<std::vector<int64_t>> &groups);
+
+  // Boundary kind of global face(s) "x-", "x+", "y-", "y+", "z-", "z+",
+  // "x", "y", "z" (both faces) or "all"; `quantities` empty = all. Same
+  // semantics and validation as the Python DistributedDomain.set_boundary
+  // (see README "Non-periodic boundaries"). PERIODIC applies to a whole
+  // axis and to every quantity; a mixed axis is rejected at realize().
+  // `value` is the FIXED constant, converted to the quantity's type
+  // (add_data<T>, or size-canonical u8/i16/f32/f64). Call before realize().
+  void set_boundary(const std::string &face, Boundary kind, double value = 0.0,
+                    const std::vector<int64_t> &quantities = {});
+  std::array<bool, 3> periodic() const;
 
   void realize();
 
@@ -96,6 +112,8 @@ public:
   // exchanged bytes per transport per full exchange (all groups)
   int64_t bytes_translate() const { return bytesTranslate_; }
   int64_t bytes_wire() const { return bytesWire_; }
+  // bytes written by one full boundary fill (all groups)
+  int64_t boundary_bytes() const { return bytesBoundary_; }
 
   // dump each local subdomain interior as CSV 'Z,Y,X,q0,q1,...'
   // (reference src/stencil.cu:1188-1264; same format as the Python
@@ -108,6 +126,23 @@ public:
 
 private:
   void gather_slots_(std::vector<Slot> &slots);
+  void validate_boundary_() const;
+  void register_boundary_(std::vector<std::string> &planLines);
+  struct FaceBc {
+    Boundary kind = Boundary::PERIODIC;
+    double value = 0.0;
+  };
+  // requests in call order (quantities may be added after set_boundary)
+  struct BcRequest {
+    std::vector<int> faces;
+    FaceBc bc;
+    std::vector<int64_t> quantities;
+  };
+  // resolved per quantity, per face (2 * axis + side)
+  std::vector<std::array<FaceBc, 6>> resolve_boundary_() const;
+  std::vector<BcRequest> bcRequests_;
+  std::vector<bool> isFloat_, isSigned_;
+  int64_t bytesBoundary_ = 0;
 
   Vec3 size_;
   Radius radius_ = Radius::constant(0);

@@ -17,9 +17,12 @@
 // per-iteration rebuild or graph re-capture is needed.
 #pragma once
 
+#include <array>
 #include <cstdint>
+#include <initializer_list>
 #include <map>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -65,8 +68,70 @@ struct CopyBatch {
   void destroy();
 };
 
+// Physical (non-periodic) boundary kinds of a global face. PERIODIC is a
+// property of a whole axis; the others may differ per face and quantity.
+enum class Boundary : int {
+  PERIODIC = 0,   // wrap (today's behaviour; the exchange fills the halo)
+  OPEN = 1,       // the library never touches these halo cells
+  FIXED = 2,      // halo = constant
+  CLAMP = 3,      // halo = nearest interior cell (zero gradient)
+  MIRROR = 4,     // halo[-1-k] = interior[k] (cell-centred zero flux)
+  ANTIMIRROR = 5, // halo[-1-k] = -interior[k] (cell-centred zero value)
+};
+
+// One axis of a boundary-fill job, in allocation coordinates of the
+// job's domain: `origin` is the allocation coordinate of global cell 0
+// on this axis and `extent` the global size N, so the global domain is
+// [origin, origin + extent). `kind` is the boundary kind of the face the
+// job's region lies outside of (PERIODIC = identity on this axis).
+struct BoundaryAxis {
+  Boundary kind = Boundary::PERIODIC;
+  int64_t origin = 0, extent = 0;
+};
+
+// One halo region of one quantity re-imposed by the boundary fill.
+// Source and destination live in the SAME buffer (base = *slot, the
+// domain's curr table, so the table survives swap() and graph replay).
+struct FillJob {
+  char *const *slot;
+  int64_t dstOff;        // byte offset of the region start
+  int64_t srcOff;        // byte offset of the source of word (0,0,0)
+  int64_t pitch, plane;  // destination byte strides (y rows / z planes)
+  int64_t srcSx, srcSy, srcSz; // signed source byte strides per word/row/plane
+  int64_t nWords;        // total words in the region
+  int32_t extXw;         // row length in words
+  int32_t extY;
+  int32_t wordBytes;     // 1/2/4/8/16
+  int32_t broadcast;     // 1: store `pat`; 0: copy source ^ `pat`
+  uint64_t pat[2];       // element pattern / sign-bit mask, replicated to 16 B
+};
+
+// All boundary-fill jobs of one exchange group on one device: ONE launch.
+struct FillBatch {
+  int dev = -1;
+  std::vector<FillJob> jobs;
+  std::vector<int64_t> prefix;
+  FillJob *dJobs = nullptr;
+  int64_t *dPrefix = nullptr;
+  int64_t nBlocks = 0;
+
+  void finalize_upload();
+  void launch_plain(hipStream_t stream); // legal inside stream capture
+  void destroy();
+};
+
+namespace detail {
+// largest word size (<=16) honoring every alignment constraint of a copy
+int pick_word(int64_t rowBytes, std::initializer_list<int64_t> alignedQuantities);
+// block ranges of a job table (prefix[i] = first block of job i) under the
+// shared ~512-block cap; returns the total block count
+int64_t block_prefix(const std::vector<int64_t> &nWords, std::vector<int64_t> &prefix);
+} // namespace detail
+
 class ExchangeEngine {
 public:
+  static constexpr int kMaxExchangeGroups = 4;
+
   explicit ExchangeEngine(std::vector<std::shared_ptr<LocalDomain>> domains);
   ~ExchangeEngine();
 
@@ -114,6 +179,18 @@ public:
   void add_unpack(int dom, int64_t buf, int64_t offset, const Vec3 &pos, const Vec3 &ext,
                   int64_t qi, int group = 0);
 
+  //// physical boundaries (csrc/src/boundary.hip)
+  // re-impose the boundary on halo region [dstPos, dstPos + ext) of
+  // quantity qi of `dom`'s curr buffer every exchange of `group`. The
+  // region must lie entirely outside the global domain on every axis whose
+  // kind is not PERIODIC. `value` holds the FIXED constant as elem_size
+  // bytes; `signWidth` is the IEEE float width in bytes whose sign bit
+  // ANTIMIRROR flips (0 when no axis is ANTIMIRROR). Returns the bytes
+  // the job writes per fill (0: an OPEN face leaves the region untouched).
+  int64_t add_boundary_fill(int dom, int64_t qi, const Vec3 &dstPos, const Vec3 &ext,
+                            const std::array<BoundaryAxis, 3> &axes, const std::string &value,
+                            int signWidth, int group = 0);
+
   // build + upload the per-GPU job tables
   void finalize();
 
@@ -127,6 +204,13 @@ public:
   void launch_unpacks_plain_on(uintptr_t stream, int group = 0);
   void launch_packs(int group = 0);
   void launch_unpacks(int group = 0);
+  // one boundary_fill launch per GPU for exchange group `group`, on the
+  // pack stream, event-ordered after every translate of the group (all
+  // devices' comm streams) and stream-ordered after the unpacks already
+  // enqueued there; covered by the host sync of sync_packs/sync_all
+  void launch_boundary(int group = 0);
+  // plain launches on a caller-owned stream (whole-step graph capture)
+  void launch_boundary_plain_on(uintptr_t stream, int group = 0);
   // stream-order every device's group-unpacks after every device's
   // group-packs (events across pack streams) -- needed when a pack on
   // one GPU fills a staging buffer that another GPU's unpack drains
@@ -204,6 +288,9 @@ private:
   std::vector<RemoteView> views_;
   std::vector<Buffer> buffers_;
   std::vector<TranslateSpec> translateSpecs_;
+  std::map<std::pair<int, int>, FillBatch> fillPending_; // (group, gpu), until finalize
+  std::vector<FillBatch> fillBatches_[kMaxExchangeGroups];
+  std::map<int, hipEvent_t> boundaryEvents_; // per device: translate -> fill
   std::vector<PackSpec> packSpecs_;
 
   std::map<int, hipStream_t> commStreams_; // per device: translate launches

@@ -11,6 +11,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <map>
 #include <set>
 #include <tuple>
@@ -52,11 +53,23 @@ inline bool dir_less(const Vec3 &a, const Vec3 &b) {
   return std::make_tuple(a.z, a.y, a.x) < std::make_tuple(b.z, b.y, b.x);
 }
 
-// plan all messages `rank` participates in (mirrors planning.plan_exchange)
+// plan all messages `rank` participates in (mirrors planning.plan_exchange).
+// On a non-periodic axis no message is planned whose neighbor index would
+// leave [0, dim): neither its send nor its recv side.
 inline ExchangePlan plan_exchange(const Placement &placement, const Radius &radius, int rank,
-                                  HaloExtentFn haloExtent) {
+                                  HaloExtentFn haloExtent,
+                                  std::array<bool, 3> periodic = {true, true, true}) {
   ExchangePlan plan;
   const Vec3 dim = placement.dim();
+  // wrapped neighbor index; false off a non-periodic edge
+  auto neighbor = [&](const Vec3 &idx, const Vec3 &d, Vec3 &out) {
+    for (int i = 0; i < 3; ++i) {
+      const int64_t c = idx[i] + d[i];
+      if (!periodic[i] && (c < 0 || c >= dim[i])) return false;
+      out[i] = (c + dim[i]) % dim[i];
+    }
+    return true;
+  };
   using Key = std::tuple<int, int64_t, int64_t>; // (peer_rank, src_gid, dst_gid)
   std::map<Key, WirePlanItem> sends, recvs;
 
@@ -72,11 +85,12 @@ inline ExchangePlan plan_exchange(const Placement &placement, const Radius &radi
           const Vec3 d(dx, dy, dz), neg(-dx, -dy, -dz);
 
           // --- send to the neighbor at +d ---
-          const Vec3 dstIdx((myIdx.x + dx + dim.x) % dim.x, (myIdx.y + dy + dim.y) % dim.y,
-                            (myIdx.z + dz + dim.z) % dim.z);
-          const int64_t dstGid = placement.linearize(dstIdx);
-          const int dstRank = placement.get_rank(dstIdx);
-          const Vec3 sExt = haloExtent(neg, placement.subdomain_size(dstIdx), radius);
+          Vec3 dstIdx, srcIdx;
+          const bool sendOk = neighbor(myIdx, d, dstIdx);
+          const int64_t dstGid = sendOk ? placement.linearize(dstIdx) : -1;
+          const int dstRank = sendOk ? placement.get_rank(dstIdx) : -1;
+          const Vec3 sExt =
+              sendOk ? haloExtent(neg, placement.subdomain_size(dstIdx), radius) : Vec3(0, 0, 0);
           if (sExt.x * sExt.y * sExt.z != 0) { // degenerate halos skipped
             if (dstRank == rank) {
               plan.translates.push_back({li, placement.get_subdomain_id(dstIdx), d, sExt});
@@ -90,8 +104,7 @@ inline ExchangePlan plan_exchange(const Placement &placement, const Radius &radi
           }
 
           // --- recv from the neighbor at -d (message travels in +d) ---
-          const Vec3 srcIdx((myIdx.x - dx + dim.x) % dim.x, (myIdx.y - dy + dim.y) % dim.y,
-                            (myIdx.z - dz + dim.z) % dim.z);
+          if (!neighbor(myIdx, neg, srcIdx)) continue;
           const int64_t srcGid = placement.linearize(srcIdx);
           const int srcRank = placement.get_rank(srcIdx);
           const Vec3 rExt = haloExtent(neg, placement.subdomain_size(myIdx), radius);

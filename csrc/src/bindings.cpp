@@ -6,6 +6,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <cstring>
 #include <memory>
 
@@ -217,6 +218,14 @@ PYBIND11_MODULE(_C, m) {
     return LocalDomain::halo_extent(dir, sz, r);
   });
 
+  py::enum_<Boundary>(m, "Boundary")
+      .value("PERIODIC", Boundary::PERIODIC)
+      .value("OPEN", Boundary::OPEN)
+      .value("FIXED", Boundary::FIXED)
+      .value("CLAMP", Boundary::CLAMP)
+      .value("MIRROR", Boundary::MIRROR)
+      .value("ANTIMIRROR", Boundary::ANTIMIRROR);
+
   py::class_<ExchangeEngine>(m, "ExchangeEngine")
       .def(py::init<std::vector<std::shared_ptr<LocalDomain>>>())
       .def("enable_peer_all", &ExchangeEngine::enable_peer_all)
@@ -249,6 +258,20 @@ PYBIND11_MODULE(_C, m) {
            [](ExchangeEngine &e, int openDev, py::bytes handle, int64_t bytes) {
              return e.open_remote_buffer(openDev, std::string(handle), bytes);
            })
+      .def("add_boundary_fill",
+           [](ExchangeEngine &e, int dom, int64_t qi, const Vec3 &dstPos, const Vec3 &ext,
+              const std::vector<std::tuple<Boundary, int64_t, int64_t>> &axes, py::bytes value,
+              int signWidth, int group) {
+             if (axes.size() != 3) throw std::runtime_error("add_boundary_fill: want 3 axes");
+             std::array<BoundaryAxis, 3> ax;
+             for (int a = 0; a < 3; ++a)
+               ax[a] = {std::get<0>(axes[a]), std::get<1>(axes[a]), std::get<2>(axes[a])};
+             return e.add_boundary_fill(dom, qi, dstPos, ext, ax, std::string(value), signWidth,
+                                        group);
+           },
+           py::arg("dom"), py::arg("qi"), py::arg("dst_pos"), py::arg("ext"), py::arg("axes"),
+           py::arg("value") = py::bytes(""), py::arg("sign_width") = 0, py::arg("group") = 0)
+      .def("launch_boundary", &ExchangeEngine::launch_boundary, py::arg("group") = 0)
       .def("finalize", &ExchangeEngine::finalize)
       .def("launch_translates", &ExchangeEngine::launch_translates, py::arg("group") = 0)
       .def("launch_packs", &ExchangeEngine::launch_packs, py::arg("group") = 0)
@@ -345,7 +368,7 @@ PYBIND11_MODULE(_C, m) {
       "cpp_plan",
       [](const Vec3 &size, const Radius &radius, int rank,
          const std::vector<std::tuple<int, int, int, int>> &slotTuples,
-         const std::string &strategy) {
+         const std::string &strategy, const std::array<bool, 3> &periodic) {
         std::vector<Slot> slots;
         for (auto &t : slotTuples)
           slots.push_back({std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)});
@@ -359,7 +382,7 @@ PYBIND11_MODULE(_C, m) {
           p = std::make_unique<NodeAwarePlacement>(size, radius, slots, haloExtent);
         else
           throw std::runtime_error("cpp_plan: unknown strategy " + strategy);
-        const ExchangePlan plan = plan_exchange(*p, radius, rank, haloExtent);
+        const ExchangePlan plan = plan_exchange(*p, radius, rank, haloExtent, periodic);
         const auto seq = pair_seq_tags(plan);
 
         auto tup3 = [](const Vec3 &v) { return py::make_tuple(v.x, v.y, v.z); };
@@ -393,7 +416,8 @@ PYBIND11_MODULE(_C, m) {
         return out;
       },
       py::arg("size"), py::arg("radius"), py::arg("rank"), py::arg("slots"),
-      py::arg("strategy") = "node_aware");
+      py::arg("strategy") = "node_aware",
+      py::arg("periodic") = std::array<bool, 3>{true, true, true});
 
   m.def("cpp_wire_layout", [](const std::vector<std::tuple<py::tuple, int64_t, int64_t, py::tuple>> &msgs,
                               const std::vector<int64_t> &elemSizes,
@@ -425,6 +449,18 @@ PYBIND11_MODULE(_C, m) {
       .def("set_placement_trivial",
            [](DistributedDomain &d) { d.set_placement(PlacementStrategy::Trivial); })
       .def("set_exchange_groups", &DistributedDomain::set_exchange_groups)
+      .def("set_boundary",
+           [](DistributedDomain &d, const std::string &face, Boundary kind, double value,
+              const std::vector<int64_t> &quantities) {
+             try {
+               d.set_boundary(face, kind, value, quantities);
+             } catch (const std::invalid_argument &e) {
+               throw py::value_error(e.what());
+             }
+           },
+           py::arg("face"), py::arg("kind"), py::arg("value") = 0.0,
+           py::arg("quantities") = std::vector<int64_t>{})
+      .def("boundary_bytes", &DistributedDomain::boundary_bytes)
       .def("realize", &DistributedDomain::realize)
       .def("exchange", &DistributedDomain::exchange, py::arg("group") = 0)
       .def("swap", &DistributedDomain::swap)

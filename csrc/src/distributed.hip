@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <stdexcept>
@@ -92,6 +93,9 @@ DistributedDomain::DistributedDomain(int64_t x, int64_t y, int64_t z) : size_(x,
 
 int64_t DistributedDomain::add_data(int64_t elemSize, const std::string &name) {
   data_.emplace_back(elemSize, name);
+  // size-canonical interpretation (fp32/fp64/int16/u8), as write_paraview
+  isFloat_.push_back(elemSize == 4 || elemSize == 8);
+  isSigned_.push_back(elemSize != 1);
   return (int64_t)data_.size() - 1;
 }
 
@@ -101,6 +105,150 @@ void DistributedDomain::set_exchange_groups(const std::vector<std::vector<int64_
   if (groups.size() > 4) throw std::runtime_error("at most 4 exchange groups");
   groups_ = groups;
   for (auto &g : groups_) std::sort(g.begin(), g.end());
+}
+
+void DistributedDomain::set_boundary(const std::string &face, Boundary kind, double value,
+                                     const std::vector<int64_t> &quantities) {
+  if (realized_) throw std::invalid_argument("set_boundary must be called before realize()");
+  static const char *names[6] = {"x-", "x+", "y-", "y+", "z-", "z+"};
+  BcRequest req;
+  for (int f = 0; f < 6; ++f)
+    if (face == names[f] || face == "all" || (face.size() == 1 && face[0] == names[f][0]))
+      req.faces.push_back(f);
+  if (req.faces.empty()) throw std::invalid_argument("set_boundary: unknown face '" + face + "'");
+  if (kind == Boundary::PERIODIC && !quantities.empty())
+    throw std::invalid_argument("set_boundary: PERIODIC applies to all quantities");
+  req.bc = {kind, value};
+  req.quantities = quantities;
+  bcRequests_.push_back(std::move(req));
+}
+
+std::vector<std::array<DistributedDomain::FaceBc, 6>> DistributedDomain::resolve_boundary_() const {
+  std::vector<std::array<FaceBc, 6>> out(data_.size());
+  for (const BcRequest &r : bcRequests_) {
+    std::vector<int64_t> qis = r.quantities;
+    if (qis.empty())
+      for (int64_t qi = 0; qi < (int64_t)data_.size(); ++qi) qis.push_back(qi);
+    for (int64_t qi : qis) {
+      if (qi < 0 || qi >= (int64_t)data_.size())
+        throw std::invalid_argument("set_boundary: bad quantity index");
+      for (int f : r.faces) out[qi][f] = r.bc;
+    }
+  }
+  return out;
+}
+
+std::array<bool, 3> DistributedDomain::periodic() const {
+  const auto bc = resolve_boundary_();
+  std::array<bool, 3> per = {true, true, true};
+  for (int a = 0; a < 3; ++a) {
+    int nPer = 0, nNon = 0;
+    for (const auto &q : bc)
+      for (int side = 0; side < 2; ++side)
+        (q[2 * a + side].kind == Boundary::PERIODIC ? nPer : nNon)++;
+    if (nPer && nNon)
+      throw std::invalid_argument(
+          std::string("boundary: axis ") + "xyz"[a] +
+          " mixes PERIODIC with non-periodic faces (periodicity is per axis, all quantities)");
+    per[a] = nNon == 0;
+  }
+  return per;
+}
+
+void DistributedDomain::validate_boundary_() const {
+  const auto bc = resolve_boundary_();
+  const std::array<bool, 3> per = periodic();
+  const Vec3 dim = placement_->dim();
+  for (int a = 0; a < 3; ++a) {
+    if (per[a]) continue;
+    int64_t minExt = size_[a];
+    for (int64_t i = 0; i < dim[a]; ++i) {
+      Vec3 idx(0, 0, 0);
+      idx[a] = i;
+      minExt = std::min(minExt, placement_->subdomain_size(idx)[a]);
+    }
+    for (size_t qi = 0; qi < bc.size(); ++qi)
+      for (int side = 0; side < 2; ++side) {
+        const Boundary k = bc[qi][2 * a + side].kind;
+        const int64_t r = a == 0   ? radius_.x(side ? 1 : -1)
+                          : a == 1 ? radius_.y(side ? 1 : -1)
+                                   : radius_.z(side ? 1 : -1);
+        if ((k == Boundary::MIRROR || k == Boundary::ANTIMIRROR) && r > minExt)
+          throw std::invalid_argument("boundary: MIRROR/ANTIMIRROR face radius exceeds the "
+                                      "smallest subdomain extent on that axis");
+        if (k == Boundary::CLAMP && minExt < 1)
+          throw std::invalid_argument("boundary: CLAMP on an empty extent");
+        if (k == Boundary::ANTIMIRROR &&
+            !(isFloat_[qi] && (data_[qi].first == 2 || data_[qi].first == 4 ||
+                               data_[qi].first == 8)))
+          throw std::invalid_argument("boundary: ANTIMIRROR needs an IEEE float quantity");
+      }
+  }
+}
+
+namespace {
+// the FIXED constant as the quantity's element bytes
+std::string value_bytes(double v, int64_t es, bool isFloat, bool isSigned) {
+  std::string out((size_t)es, '\0');
+  auto put = [&](auto x) { std::memcpy(&out[0], &x, sizeof(x)); };
+  if (isFloat && es == 8) put((double)v);
+  else if (isFloat && es == 4) put((float)v);
+  else if (es == 8) put((int64_t)v);
+  else if (es == 4) put((int32_t)v);
+  else if (es == 2) put((int16_t)v);
+  else if (isSigned) put((int8_t)v);
+  else put((uint8_t)v);
+  return out;
+}
+} // namespace
+
+void DistributedDomain::register_boundary_(std::vector<std::string> &planLines) {
+  const std::array<bool, 3> per = periodic();
+  if (per[0] && per[1] && per[2]) return;
+  const auto bc = resolve_boundary_();
+  for (size_t g = 0; g < groups_.size(); ++g)
+    for (int li = 0; li < (int)domains_.size(); ++li) {
+      LocalDomain &dom = *domains_[li];
+      const Vec3 lo = dom.origin(), hi = dom.origin() + dom.size();
+      const Vec3 full = dom.full_region().lo;
+      for (int dz = -1; dz <= 1; ++dz)
+        for (int dy = -1; dy <= 1; ++dy)
+          for (int dx = -1; dx <= 1; ++dx) {
+            const Vec3 d(dx, dy, dz);
+            if ((dx == 0 && dy == 0 && dz == 0) || radius_.dir(dx, dy, dz) == 0) continue;
+            bool out[3];
+            bool any = false;
+            for (int a = 0; a < 3; ++a) {
+              out[a] = !per[a] && ((d[a] < 0 && lo[a] == 0) || (d[a] > 0 && hi[a] == size_[a]));
+              any = any || out[a];
+            }
+            if (!any) continue;
+            const Vec3 ext = dom.halo_extent(d);
+            if (ext.flatten() == 0) continue;
+            int64_t bytes = 0;
+            for (int64_t qi : groups_[g]) {
+              std::array<BoundaryAxis, 3> axes;
+              std::string value;
+              int signWidth = 0;
+              // the walk is z, y, x: the first FIXED face met supplies the value
+              for (int a = 2; a >= 0; --a) {
+                if (!out[a]) continue;
+                const FaceBc &f = bc[qi][2 * a + (d[a] > 0 ? 1 : 0)];
+                axes[a] = {f.kind, -full[a], size_[a]};
+                if (f.kind == Boundary::FIXED && value.empty())
+                  value = value_bytes(f.value, data_[qi].first, isFloat_[qi], isSigned_[qi]);
+                if (f.kind == Boundary::ANTIMIRROR) signWidth = (int)data_[qi].first;
+              }
+              bytes += engine_->add_boundary_fill(li, qi, dom.halo_pos(d, true), ext, axes, value,
+                                                  signWidth, (int)g);
+            }
+            bytesBoundary_ += bytes;
+            char line[160];
+            snprintf(line, sizeof(line), "boundary_fill dir=(%d, %d, %d) local=%d group=%d bytes=%lld\n",
+                     dx, dy, dz, li, (int)g, (long long)bytes);
+            planLines.push_back(line);
+          }
+    }
 }
 
 void DistributedDomain::gather_slots_(std::vector<Slot> &slots) {
@@ -193,7 +341,9 @@ void DistributedDomain::realize() {
   setupTimes_["realize"] = secs(t0, now());
   t0 = now();
 
-  const ExchangePlan plan = plan_exchange(*placement_, radius_, rank_, &halo_extent_of);
+  validate_boundary_();
+  const ExchangePlan plan =
+      plan_exchange(*placement_, radius_, rank_, &halo_extent_of, periodic());
   setupTimes_["plan"] = secs(t0, now());
   t0 = now();
   std::vector<int64_t> elemSizes;
@@ -249,6 +399,8 @@ void DistributedDomain::realize() {
       }
     }
   }
+  std::vector<std::string> boundaryLines;
+  register_boundary_(boundaryLines);
   engine_->finalize();
 
   bool anyWire = false;
@@ -309,6 +461,7 @@ void DistributedDomain::realize() {
           fprintf(f, "rccl_recv dir=(%lld, %lld, %lld) src_rank=%d src_gid=%lld dst_gid=%lld bytes=%lld\n",
                   (long long)m.dir.x, (long long)m.dir.y, (long long)m.dir.z, it.peerRank,
                   (long long)m.srcGid, (long long)m.dstGid, (long long)(m.volume() * esTotal2));
+      for (const std::string &l : boundaryLines) fputs(l.c_str(), f);
       fclose(f);
     }
   }
@@ -327,6 +480,10 @@ void DistributedDomain::exchange_end(int group) {
     wire_->post(group, engine_->pack_stream_handle(wireDev_));
     engine_->launch_unpacks(3 * group);
   }
+  // physical boundaries: after every inbound halo write of the group
+  // (event-ordered behind the translates, stream-ordered behind the
+  // unpacks), before the one host sync
+  engine_->launch_boundary(group);
   engine_->sync_all();
 }
 

@@ -69,6 +69,10 @@ __global__ void copy_batch_kernel(const CopyJob *__restrict__ jobs, const int64_
   }
 }
 
+} // namespace
+
+namespace detail {
+
 // largest word size (<=16) honoring every alignment constraint of the copy
 int pick_word(int64_t rowBytes, std::initializer_list<int64_t> alignedQuantities) {
   for (int w : {16, 8, 4, 2}) {
@@ -84,9 +88,7 @@ int pick_word(int64_t rowBytes, std::initializer_list<int64_t> alignedQuantities
   return 1;
 }
 
-} // namespace
-
-void CopyBatch::finalize_upload() {
+int64_t block_prefix(const std::vector<int64_t> &nWords, std::vector<int64_t> &prefix) {
   // Cap the batch at ~512 blocks (grid-stride covers the rest): a halo
   // exchange overlapped with compute need not flood all 256 CUs. One
   // measurement showed +8.6% on the jacobi step, a re-measurement on
@@ -98,16 +100,25 @@ void CopyBatch::finalize_upload() {
   if (const char *e = getenv("STENCIL_AMD_COPY_DIV")) div = atoll(e);
   if (div < 1) {
     int64_t natural = 0;
-    for (const auto &j : jobs) natural += std::max<int64_t>(1, (j.nWords + kBlock - 1) / kBlock);
+    for (int64_t n : nWords) natural += std::max<int64_t>(1, (n + kBlock - 1) / kBlock);
     div = std::max<int64_t>(1, (natural + kMaxBlocks - 1) / kMaxBlocks);
   }
-  prefix.assign(jobs.size() + 1, 0);
-  for (size_t i = 0; i < jobs.size(); ++i) {
-    const int64_t blocks =
-        std::max<int64_t>(1, (jobs[i].nWords + kBlock * div - 1) / (kBlock * div));
+  prefix.assign(nWords.size() + 1, 0);
+  for (size_t i = 0; i < nWords.size(); ++i) {
+    const int64_t blocks = std::max<int64_t>(1, (nWords[i] + kBlock * div - 1) / (kBlock * div));
     prefix[i + 1] = prefix[i] + blocks;
   }
-  nBlocks = prefix.back();
+  return prefix.back();
+}
+
+} // namespace detail
+
+using detail::pick_word;
+
+void CopyBatch::finalize_upload() {
+  std::vector<int64_t> nWords;
+  for (const auto &j : jobs) nWords.push_back(j.nWords);
+  nBlocks = detail::block_prefix(nWords, prefix);
   STENCIL_HIP(hipSetDevice(dev));
   STENCIL_HIP(hipMalloc((void **)&dJobs, jobs.size() * sizeof(CopyJob)));
   STENCIL_HIP(hipMalloc((void **)&dPrefix, prefix.size() * sizeof(int64_t)));
@@ -189,6 +200,9 @@ ExchangeEngine::~ExchangeEngine() {
     for (auto &b : packBatches_[g]) b.destroy();
     for (auto &b : unpackBatches_[g]) b.destroy();
   }
+  for (auto &set : fillBatches_)
+    for (auto &b : set) b.destroy();
+  for (auto &kv : boundaryEvents_) (void)hipEventDestroy(kv.second);
   for (auto &kv : commStreams_) (void)hipStreamDestroy(kv.second);
   for (auto &kv : packStreams_) (void)hipStreamDestroy(kv.second);
   for (auto &kv : fenceEvents_) (void)hipEventDestroy(kv.second);
@@ -381,6 +395,11 @@ void ExchangeEngine::finalize() {
       b.finalize_upload();
       if (graphs) b.capture_graph();
     }
+  for (auto &kv : fillPending_) {
+    kv.second.finalize_upload();
+    fillBatches_[kv.first.first].push_back(std::move(kv.second));
+  }
+  fillPending_.clear();
   finalized_ = true;
 }
 

@@ -477,8 +477,8 @@ std::vector<std::unique_ptr<StepGraph>> g_stepGraphs;
 
 int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
                             const Rect3 &computeRegion) {
-  // whole-step replay graph: [translate copy_batch -> full-region jacobi
-  // -> device-side table swap] captured once per buffer parity. Replay
+  // whole-step replay graph: [translate copy_batch -> boundary fill (if
+  // any axis is non-periodic) -> full-region jacobi -> device-side table swap] captured once per buffer parity. Replay
   // costs one hipGraphLaunch (~5 us) instead of the ~0.25 ms of host
   // orchestration measured per step at 750^3 (exchange + launches +
   // stream syncs + swap upload). Single-process single-domain only (the
@@ -492,6 +492,9 @@ int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect
   for (int par = 0; par < 2; ++par) {
     STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
     eng.launch_translates_plain_on((uintptr_t)sg->stream, 0);
+    // physical boundaries (no-op on a fully periodic domain): the fill
+    // reads halos the translates delivered, same stream so ordered
+    eng.launch_boundary_plain_on((uintptr_t)sg->stream, 0);
     // the graph's region is the whole interior rect: pure-vector launch
     // (scalar tail lanes measured ~10% of the kernel in the probe)
     launch_jacobi_on(d, qi, region, computeRegion, sg->stream, /*fullRectVec=*/1);
@@ -535,6 +538,7 @@ int64_t jacobi_graph_create_overlap(ExchangeEngine &eng, int dom, int64_t qi,
     STENCIL_HIP(hipEventRecord(evF, sg->stream));
     STENCIL_HIP(hipStreamWaitEvent(stream2, evF, 0));
     eng.launch_translates_plain_on((uintptr_t)stream2, 0); // halos || interior
+    eng.launch_boundary_plain_on((uintptr_t)stream2, 0);   // after the translates it reads
     launch_jacobi_on(d, qi, interior, computeRegion, sg->stream, /*fullRectVec=*/1);
     STENCIL_HIP(hipEventRecord(evJ, stream2));
     STENCIL_HIP(hipStreamWaitEvent(sg->stream, evJ, 0));

@@ -48,6 +48,7 @@ except ImportError as e:  # pragma: no cover
     ) from e
 
 from ._C import Radius, Rect3, Vec3, prime_factors
+from .boundary import Boundary
 from .core import DataHandle, DistributedDomain, Method
 from .parallel.machine import Machine
 from .parallel.placement import PlacementStrategy
@@ -55,6 +56,7 @@ from .parallel.placement import PlacementStrategy
 __all__ = [
     "Machine",
     "DistributedDomain",
+    "Boundary",
     "DataHandle",
     "Method",
     "PlacementStrategy",

@@ -17,6 +17,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _C
+from .boundary import Boundary, make_spec, parse_face
 from .parallel.comm import Comm
 from .parallel.placement import PlacementStrategy, gather_slots, make_placement
 from .parallel.planning import plan_exchange
@@ -97,6 +98,11 @@ class DistributedDomain:
         self._realized = False
         # per-method exchanged bytes (one full exchange)
         self.bytes_by_method: Dict[str, int] = {"direct_kernel": 0, "rccl": 0, "ipc_kernel": 0}
+        # physical boundaries (set_boundary): requests resolve at realize()
+        self._bc_requests: List[tuple] = []
+        self.boundary = None  # BoundarySpec when some axis is non-periodic
+        self.boundary_bytes = 0  # bytes written by one full boundary fill
+        self._boundary_lines: List[str] = []
         self.time_exchange = 0.0
         self.time_swap = 0.0
         # setup-phase timers (reference STENCIL_SETUP_STATS,
@@ -150,6 +156,42 @@ class DistributedDomain:
             )
         self.exchange_groups = [sorted(g) for g in groups]
 
+    def set_boundary(self, face: str, kind: Boundary, value=0, quantities=None):
+        """boundary kind of global face(s): `face` is "x-", "x+", "y-",
+        "y+", "z-", "z+", an axis "x"/"y"/"z" (both faces) or "all".
+
+        Kinds: PERIODIC (default; a property of a whole AXIS and of all
+        quantities -- both faces of an axis are periodic or neither is),
+        and on a non-periodic axis, per face and per quantity: OPEN (the
+        library never touches those halo cells), FIXED(value), CLAMP
+        (nearest interior cell), MIRROR (halo[-1-k] = interior[k]) and
+        ANTIMIRROR (halo[-1-k] = -interior[k]; IEEE float quantities of
+        2/4/8 bytes only). Edges and corners hold what padding the global
+        array one axis at a time in the order x, y, z would give.
+
+        `quantities`: handles or indices (None = all). The halos are
+        re-imposed on the current buffer by every exchange of the
+        quantity's group. Call before realize(); later calls override
+        earlier ones. OPEN x faces do not mix with the jacobi kernel's
+        free row extension (extend_vec=1), which scribbles on next-buffer
+        x halos and relies on the exchange refreshing them."""
+        if self._realized:
+            raise ValueError("set_boundary() must be called before realize()")
+        kind = Boundary(kind)
+        faces = parse_face(face)
+        qis = None
+        if quantities is not None:
+            qis = [q.index if isinstance(q, DataHandle) else int(q) for q in quantities]
+            if kind == Boundary.PERIODIC:
+                raise ValueError("PERIODIC applies to an axis for all quantities")
+        self._bc_requests.append((faces, kind, value, qis))
+
+    @property
+    def periodic(self) -> Tuple[bool, bool, bool]:
+        """per-axis periodicity as currently configured"""
+        spec = make_spec(self.size, self._dtypes, self._bc_requests)
+        return spec.periodic if spec is not None else (True, True, True)
+
     def set_output_prefix(self, p: str):
         self.output_prefix = p
 
@@ -187,6 +229,10 @@ class DistributedDomain:
         if self.placement is None:
             self.do_placement()
         rank = self.comm.rank
+        self.boundary = make_spec(self.size, self._dtypes, self._bc_requests)
+        if self.boundary is not None:
+            self.boundary.validate(self.placement, self.radius)
+        periodic = self.boundary.periodic if self.boundary is not None else (True, True, True)
         n_local = self.placement.num_local(rank)
         specs = []
         for li in range(n_local):
@@ -212,7 +258,7 @@ class DistributedDomain:
         self.setup_times["realize"] = time.perf_counter() - t0
 
         t0 = time.perf_counter()
-        plan = plan_exchange(self.placement, self.radius, rank)
+        plan = plan_exchange(self.placement, self.radius, rank, periodic)
         self.setup_times["plan"] = time.perf_counter() - t0
         if not (self.methods & Method.DIRECT_KERNEL) and plan.translates:
             raise RuntimeError("same-rank halos require Method.DIRECT_KERNEL")
@@ -222,11 +268,14 @@ class DistributedDomain:
             "comm": self.comm,
             "placement": self.placement,
             "ipc": bool(self.methods & Method.IPC_KERNEL),
+            "boundary": self.boundary,
         }
         t0 = time.perf_counter()
         self.backend.register_plan(plan, ctx)
         self.setup_times["create"] = time.perf_counter() - t0
         self.plan = plan
+        self._boundary_lines = list(getattr(self.backend, "boundary_lines", []))
+        self.boundary_bytes = int(getattr(self.backend, "boundary_bytes", 0))
         self._count_bytes(plan)
         if self.output_prefix:
             self._write_plan_files(plan)
@@ -300,11 +349,11 @@ class DistributedDomain:
         return self.local_rect(li)[0]
 
     def get_topology(self):
-        """periodic neighbor topology over the partition grid
+        """neighbor topology over the partition grid
         (reference stencil.hpp:203)"""
         from .parallel.topology import Topology
 
-        return Topology(self.placement.dim())
+        return Topology(self.placement.dim(), self.periodic)
 
     def get_placement(self):
         return self.placement
@@ -458,6 +507,8 @@ class DistributedDomain:
                     f.write(
                         f"rccl_recv dir={m.dir} src_rank={rcv.peer_rank} src_gid={m.src_gid} dst_gid={m.dst_gid} bytes={m.volume() * es_total}\n"
                     )
+            for line in self._boundary_lines:  # only with a non-periodic axis
+                f.write(line + "\n")
         # rank-rank comm matrix (numpy loadtxt-able; rank 0 writes)
         row = [0] * self.comm.world_size
         for s in plan.sends:

@@ -25,6 +25,7 @@ class Jacobi3D:
         device: str = "cpu",
         radius: int = 1,
         halo_multiplier: int = 1,
+        boundary=None,
     ):
         """radius >= 1: halo depth (the 7-point kernel reads 1 cell; deeper
         radii exercise the deeper-halo exchange, reference jacobi3d-strong
@@ -35,7 +36,17 @@ class Jacobi3D:
         halos are allocated and exchanged m*radius deep every m-th step;
         between exchanges each step computes a region EXPANDED into the
         still-valid halo by (m-1-phase)*radius cells. Results are
-        identical to exchanging every step."""
+        identical to exchanging every step.
+
+        boundary: {face: kind | (kind, value)} forwarded to
+        DistributedDomain.set_boundary (faces "x-".."z+", "x", "y", "z",
+        "all"); None = fully periodic. OPEN is rejected: the fast
+        kernel's free row extension scribbles on next-buffer x halos and
+        relies on the exchange refreshing them, which an OPEN face never
+        does. halo_multiplier > 1 needs every axis periodic (the expanded
+        compute region would leave the global domain). With a
+        non-periodic axis the multi-rank step graphs fall back to the
+        eager path; the single-domain graph captures the fill."""
         assert halo_multiplier >= 1
         self.m = int(halo_multiplier)
         self.kernel_radius = int(radius)
@@ -46,6 +57,19 @@ class Jacobi3D:
         if gpus is not None:
             self.dd.set_gpus(gpus)
         self.h = self.dd.add_data(np.float32, "temp")
+        if boundary:
+            from ..boundary import Boundary
+
+            for face, spec in boundary.items():
+                kind, value = spec if isinstance(spec, (tuple, list)) else (spec, 0)
+                if Boundary(kind) == Boundary.OPEN:
+                    raise ValueError(
+                        "Jacobi3D does not support OPEN boundaries (the kernel's row "
+                        "extension overwrites x halos the exchange must refresh)"
+                    )
+                self.dd.set_boundary(face, kind, value)
+            if self.m > 1 and not all(self.dd.periodic):
+                raise ValueError("halo_multiplier > 1 needs every axis periodic")
 
     def realize(self):
         self.dd.realize()
@@ -104,6 +128,7 @@ class Jacobi3D:
             and getattr(self.dd.backend, "_ipc_active", False)
             and not any(getattr(self.dd.backend, "_has_wire", [True]))
             and not staged_local
+            and self.dd.boundary is None  # non-periodic: eager path (fill not captured)
         ):
             # multi-rank whole-step graphs (single-node 1-rank/GPU shape:
             # every cross-rank halo is an IPC direct write or staged thin

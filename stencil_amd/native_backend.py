@@ -68,6 +68,9 @@ class NativeBackend:
         self._colo_parity = [0] * ng
         self._staged_local = [False] * ng
         self._staging_recv = {}
+        self._has_boundary = [False] * ng
+        self.boundary_bytes = 0  # bytes one full boundary fill writes
+        self.boundary_lines: List[str] = []  # plan-file lines
 
     # ---- plan registration ----
     def register_plan(self, plan: ExchangePlan, ctx: Optional[dict] = None):
@@ -176,11 +179,65 @@ class NativeBackend:
                 else:
                     self._recv_items[g].append((buf, item.peer_rank, tag))
             self._has_wire[g] = bool(self._send_items[g] or self._recv_items[g])
+        self._register_boundary(ctx.get("boundary") if ctx else None)
         self.engine.finalize()
         if ctx is not None:
             self._setup_wire(ctx)
         elif any(self._has_wire):
             raise RuntimeError("cross-rank wire transfers need a comm context")
+
+    def _register_boundary(self, spec):
+        """physical boundaries: per exchange group, one fill job per
+        (local domain, out-pointing halo region, quantity of the group),
+        all executed by ONE boundary_fill launch per GPU per exchange
+        (csrc/src/boundary.hip). Positions are allocation coordinates."""
+        from .boundary import Boundary
+
+        self._has_boundary = [False] * len(self.groups)
+        self.boundary_bytes = 0
+        self.boundary_lines = []
+        if spec is None:
+            return
+        elem_sizes = [es for es, _ in self.data_defs]
+        for g, qis in enumerate(self.groups):
+            for li, dom in enumerate(self.domains):
+                origin = dom.origin().tuple()
+                full_lo = dom.full_region().lo.tuple()
+                for d, out in spec.out_regions(self.radius, origin, dom.size().tuple()):
+                    ext = dom.halo_extent(_vec3(d))
+                    if ext.flatten() == 0:
+                        continue
+                    pos = dom.halo_pos(_vec3(d), True)
+                    nbytes = 0
+                    for qi in sorted(qis):
+                        axes = []
+                        value = b""
+                        sign_width = 0
+                        for a in range(3):
+                            if not out[a]:
+                                axes.append((Boundary.PERIODIC, 0, 0))
+                                continue
+                            side = 1 if d[a] > 0 else 0
+                            # allocation coordinate of global cell 0, global extent
+                            axes.append((spec.kind(qi, a, side), -full_lo[a], spec.size[a]))
+                        for a in (2, 1, 0):  # the z, y, x walk stops at its first FIXED face
+                            if not out[a]:
+                                continue
+                            side = 1 if d[a] > 0 else 0
+                            k = spec.kind(qi, a, side)
+                            if k == Boundary.FIXED and not value:
+                                value = spec.value(qi, a, side).tobytes()
+                            if k == Boundary.ANTIMIRROR:
+                                sign_width = elem_sizes[qi]
+                        nbytes += self.engine.add_boundary_fill(
+                            li, qi, pos, ext, axes, value, sign_width, g
+                        )
+                    if nbytes:
+                        self._has_boundary[g] = True
+                    self.boundary_bytes += nbytes
+                    self.boundary_lines.append(
+                        f"boundary_fill dir={d} local={li} group={g} bytes={nbytes}"
+                    )
 
     def _setup_wire(self, ctx):
         """choose the cross-rank wire transport, identically on every rank
@@ -562,6 +619,12 @@ class NativeBackend:
             # host sync below
             self.engine.fence_packs_unpacks(3 * g)
             self.engine.launch_unpacks(3 * g)
+        if self._has_boundary[g] and not self._ipc_active:
+            # physical boundaries: the fill reads halos this exchange
+            # delivers, so it is event-ordered behind every translate of
+            # the group and stream-ordered behind the unpacks just
+            # enqueued on the pack stream; sync_all below covers it
+            self.engine.launch_boundary(g)
         self.engine.sync_all()
         if self._ipc_active:
             # all colocated ranks' direct writes and staged packs are
@@ -574,6 +637,10 @@ class NativeBackend:
             # the host blocks once (sync_packs), not twice.
             self._colo_barrier()
             self.engine.launch_unpacks(3 * g + 1 + self._colo_parity[g])
+            if self._has_boundary[g]:
+                # IPC peers write our halos too: fill only behind the
+                # colocated barrier and the staged unpacks (pack stream)
+                self.engine.launch_boundary(g)
             self.engine.sync_packs()
             self._colo_parity[g] ^= 1
 

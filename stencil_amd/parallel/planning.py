@@ -69,10 +69,25 @@ class ExchangePlan:
     recvs: List[WirePlanItem] = field(default_factory=list)
 
 
-def plan_exchange(placement, radius: "_C.Radius", rank: int) -> ExchangePlan:
-    """plan all messages this rank participates in"""
+def plan_exchange(placement, radius: "_C.Radius", rank: int,
+                  periodic=(True, True, True)) -> ExchangePlan:
+    """plan all messages this rank participates in. `periodic` is the
+    per-axis (x, y, z) mask: on a non-periodic axis no message is planned
+    whose neighbor index would leave [0, dim) -- neither its send nor its
+    recv side (those halos belong to the boundary fill instead)."""
     plan = ExchangePlan()
     dim = placement.dim()
+    periodic = tuple(bool(p) for p in periodic)
+
+    def neighbor(idx, d):
+        """wrapped neighbor index, or None off a non-periodic edge"""
+        out = []
+        for i in range(3):
+            c = idx[i] + d[i]
+            if not periodic[i] and not 0 <= c < dim[i]:
+                return None
+            out.append(c % dim[i])
+        return tuple(out)
     sends: Dict[Tuple[int, int, int], WirePlanItem] = {}
     recvs: Dict[Tuple[int, int, int], WirePlanItem] = {}
 
@@ -91,30 +106,33 @@ def plan_exchange(placement, radius: "_C.Radius", rank: int) -> ExchangePlan:
                     neg = (-dx, -dy, -dz)
 
                     # --- send to the neighbor at +d ---
-                    dst_idx = tuple((my_idx[i] + d[i]) % dim[i] for i in range(3))
-                    dst_gid = placement.linearize(dst_idx)
-                    dst_rank = placement.get_rank(dst_idx)
-                    dst_size = placement.subdomain_size(dst_idx)
-                    s_ext = _C.halo_extent(_vec3(neg), _vec3(dst_size), radius).tuple()
-                    if s_ext[0] * s_ext[1] * s_ext[2] == 0:
-                        # degenerate: a diagonal radius is set but a face
-                        # radius of one of its components is 0, so the halo
-                        # region has no volume (the reference fatals here,
-                        # src/packer.cu:83; we skip the empty message)
-                        continue
-                    msg = Message(d, my_gid, dst_gid, s_ext)
-                    if dst_rank == rank:
-                        plan.translates.append(
-                            TranslatePlanItem(li, placement.get_subdomain_id(dst_idx), d, s_ext)
-                        )
-                    else:
-                        key = (dst_rank, my_gid, dst_gid)
-                        if key not in sends:
-                            sends[key] = WirePlanItem(dst_rank, my_gid, dst_gid, li)
-                        sends[key].messages.append(msg)
+                    dst_idx = neighbor(my_idx, d)
+                    if dst_idx is not None:
+                        dst_gid = placement.linearize(dst_idx)
+                        dst_rank = placement.get_rank(dst_idx)
+                        dst_size = placement.subdomain_size(dst_idx)
+                        s_ext = _C.halo_extent(_vec3(neg), _vec3(dst_size), radius).tuple()
+                        if s_ext[0] * s_ext[1] * s_ext[2] == 0:
+                            # degenerate: a diagonal radius is set but a face
+                            # radius of one of its components is 0, so the halo
+                            # region has no volume (the reference fatals here,
+                            # src/packer.cu:83; we skip the empty message)
+                            continue
+                        msg = Message(d, my_gid, dst_gid, s_ext)
+                        if dst_rank == rank:
+                            plan.translates.append(
+                                TranslatePlanItem(li, placement.get_subdomain_id(dst_idx), d, s_ext)
+                            )
+                        else:
+                            key = (dst_rank, my_gid, dst_gid)
+                            if key not in sends:
+                                sends[key] = WirePlanItem(dst_rank, my_gid, dst_gid, li)
+                            sends[key].messages.append(msg)
 
                     # --- recv from the neighbor at -d (message travels in +d) ---
-                    src_idx = tuple((my_idx[i] + neg[i]) % dim[i] for i in range(3))
+                    src_idx = neighbor(my_idx, neg)
+                    if src_idx is None:
+                        continue
                     src_gid = placement.linearize(src_idx)
                     src_rank = placement.get_rank(src_idx)
                     my_size = placement.subdomain_size(my_idx)

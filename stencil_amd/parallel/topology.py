@@ -1,23 +1,32 @@
-"""Stencil neighbor topology (periodic boundary).
+"""Stencil neighbor topology (periodic by default, per-axis mask).
 
 Reference: include/stencil/topology.hpp, src/topology.cpp — neighbor lookup
 wraps the subdomain index into the partition grid.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 Vec = Tuple[int, int, int]
 
 
 class Topology:
-    """Periodic 3D torus over the partition grid of extent `dim`."""
+    """3D neighbor lookup over the partition grid of extent `dim`: a torus
+    on every periodic axis, a bounded line on the others."""
 
-    def __init__(self, dim: Vec):
+    def __init__(self, dim: Vec, periodic=(True, True, True)):
         self.dim = tuple(int(c) for c in dim)
+        self.periodic = tuple(bool(p) for p in periodic)
 
-    def get_neighbor(self, idx: Vec, direction: Vec) -> Vec:
-        return tuple((idx[i] + direction[i]) % self.dim[i] for i in range(3))
+    def get_neighbor(self, idx: Vec, direction: Vec) -> Optional[Vec]:
+        """wrapped neighbor index; None off a non-periodic edge"""
+        out = []
+        for i in range(3):
+            c = idx[i] + direction[i]
+            if not self.periodic[i] and not 0 <= c < self.dim[i]:
+                return None
+            out.append(c % self.dim[i])
+        return tuple(out)
 
 
 DIRECTIONS = [

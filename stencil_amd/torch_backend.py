@@ -92,8 +92,13 @@ class TorchBackend:
         self._translates = [[] for _ in range(ng)]
         self._send_bufs = [[] for _ in range(ng)]  # per group
         self._recv_bufs = [[] for _ in range(ng)]
+        self._boundary = None
+        self.boundary_bytes = 0
+        self.boundary_lines = []
 
     def register_plan(self, plan: ExchangePlan, ctx=None):
+        self._boundary = ctx.get("boundary") if ctx else None
+        self._plan_boundary()
         elem_sizes = [es for es, _ in self.data_defs]
         seq = pair_seq_tags(plan)
         ng = len(self.groups)
@@ -156,6 +161,86 @@ class TorchBackend:
             for w in dist.batch_isend_irecv(ops):
                 w.wait()
             self._unpack(g)
+        if self._boundary is not None:
+            self._fill_boundary(g)
+
+    # ---- physical boundaries ----
+    def _plan_boundary(self):
+        """the fill as a list of tensor-slicing passes, in the DEFINING
+        order: axis x, then y, then z, each pass over everything the
+        earlier passes produced. A region that also points out of the
+        domain on a LATER non-periodic axis is left to that axis's pass."""
+        from .boundary import Boundary
+
+        spec = self._boundary
+        ng = len(self.groups)
+        self._fills = [[] for _ in range(ng)]
+        self.boundary_bytes = 0
+        self.boundary_lines = []
+        if spec is None:
+            return
+        for g, qis in enumerate(self.groups):
+            for li, dom in enumerate(self.domains):
+                regions = list(spec.out_regions(self.radius, dom.origin, dom.size))
+                written = {d: 0 for d, _ in regions}
+                for a in range(3):  # pass order x, y, z
+                    for d, out in regions:
+                        if not out[a] or any(out[b] for b in range(a + 1, 3)):
+                            continue
+                        ext = dom.halo_extent(d)
+                        if ext[0] * ext[1] * ext[2] == 0:
+                            continue
+                        pos = dom.halo_pos(d, True)
+                        side = 1 if d[a] > 0 else 0
+                        # allocation coordinate of the first/last global cell on axis a
+                        g0 = -dom.full_lo()[a]
+                        edge = g0 + spec.size[a] - 1 if side else g0
+                        for qi in sorted(qis):
+                            k = spec.kind(qi, a, side)
+                            if k == Boundary.OPEN:
+                                continue
+                            self._fills[g].append(
+                                (li, qi, a, side, k, spec.value(qi, a, side), pos, ext, edge)
+                            )
+                            written[d] += ext[0] * ext[1] * ext[2] * dom.elem_sizes[qi]
+                for d, nbytes in written.items():
+                    self.boundary_bytes += nbytes
+                    self.boundary_lines.append(
+                        f"boundary_fill dir={d} local={li} group={g} bytes={nbytes}"
+                    )
+
+    _SIGN_VIEW = {2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+    def _fill_boundary(self, g):
+        from .boundary import Boundary
+
+        for li, qi, a, side, k, value, pos, ext, edge in self._fills[g]:
+            dom = self.domains[li]
+            dst = dom.region(qi, pos, ext)
+            tdim = 2 - a  # tensors are (z, y, x)
+            if k == Boundary.FIXED:
+                # bit pattern, not a numeric cast: a 2-byte float quantity
+                # lives in an int16 tensor here
+                pat = torch.frombuffer(bytearray(value.tobytes()), dtype=dst.dtype)
+                dst.copy_(pat.to(dst.device).expand(dst.shape))
+                continue
+            # source slab: same range as dst on the other axes
+            spos, sext = list(pos), list(ext)
+            if k == Boundary.CLAMP:
+                spos[a], sext[a] = edge, 1
+                src = dom.region(qi, spos, sext).expand(ext[2], ext[1], ext[0])
+                dst.copy_(src.clone())
+                continue
+            # MIRROR / ANTIMIRROR: the r interior cells next to the face, reversed
+            spos[a] = edge - ext[a] + 1 if side else edge
+            src = dom.region(qi, spos, sext).flip(tdim)
+            if k == Boundary.ANTIMIRROR:
+                # IEEE negation is a sign-bit flip: do it on the integer view
+                # so the result is bitwise-defined for every float width
+                iv = self._SIGN_VIEW[dom.elem_sizes[qi]]
+                src = src.contiguous().view(iv)
+                src = (src ^ torch.iinfo(iv).min).view(dst.dtype)
+            dst.copy_(src)
 
     def swap(self):
         for d in self.domains:
