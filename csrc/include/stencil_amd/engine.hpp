@@ -249,6 +249,31 @@ public:
   LocalDomain &domain(int i) { return *domains_[i]; }
   int num_domains() const { return (int)domains_.size(); }
 
+  // true when exchange group `group` is nothing but ONE domain's periodic
+  // self-wrap of quantity qi on every axis: a single local domain, no
+  // remote views, staging buffers, packs or boundary fills, and self
+  // translates that together cover the whole halo shell. Every halo cell
+  // is then a copy of an interior cell of the same buffer, which is what
+  // lets a stencil kernel read the wrapped neighbour itself (see
+  // csrc/src/jacobi.hip, jacobi_graph_create).
+  bool self_wrap_only(int64_t qi, int group = 0) const {
+    if (!finalized_ || domains_.size() != 1 || !views_.empty() || !buffers_.empty() ||
+        !packSpecs_.empty())
+      return false;
+    for (const auto &set : fillBatches_)
+      if (!set.empty()) return false;
+    int64_t covered = 0;
+    for (const auto &t : translateSpecs_) {
+      if (t.group != group) continue;
+      if (t.dstIsView || t.srcDom != 0 || t.dstDom != 0) return false;
+      bool has = t.qis.empty();
+      for (int64_t q : t.qis) has = has || q == qi;
+      if (has) covered += t.ext.flatten();
+    }
+    const LocalDomain &d = *domains_[0];
+    return covered == d.raw_size().flatten() - d.size().flatten();
+  }
+
 private:
   struct Buffer {
     char *ptr = nullptr;

@@ -28,6 +28,11 @@ void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, flo
 // captured once per buffer parity, replayed per step (~5 us host cost vs
 // ~0.25 ms of per-step orchestration). launch() enqueues nSteps replays
 // (alternating parities, host mirrors flipped); sync() blocks on them.
+// A fully periodic single domain gets the wrap graph instead: the stencil
+// kernel alone, reading periodic neighbours from the far side of the
+// buffer (no translate, no in-graph swap; STENCIL_JAC_WRAP=0 turns it
+// off). Halos are then stale after a step until the next exchange.
+// jacobi_graph_is_wrap() tells which graph a handle holds.
 int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
                             const Rect3 &computeRegion);
 // overlap variant: translate forked concurrent with the interior kernel
@@ -37,6 +42,7 @@ int64_t jacobi_graph_create_overlap(ExchangeEngine &eng, int dom, int64_t qi,
                                     const std::vector<Rect3> &exteriors);
 void jacobi_graph_launch(int64_t handle, int64_t nSteps);
 void jacobi_graph_sync(int64_t handle);
+bool jacobi_graph_is_wrap(int64_t handle);
 
 // Multi-rank whole-step graphs (see csrc/src/jacobi.hip): per parity,
 // A = [interior + translates + staged packs], B = [staged unpacks +

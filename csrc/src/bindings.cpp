@@ -318,6 +318,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("exteriors"));
   m.def("jacobi_graph_launch", &jacobi_graph_launch, py::arg("handle"), py::arg("n_steps") = 1);
   m.def("jacobi_graph_sync", &jacobi_graph_sync);
+  m.def("jacobi_graph_is_wrap", &jacobi_graph_is_wrap);
   m.def("jacobi_mr_graph_create", &jacobi_mr_graph_create, py::arg("eng"), py::arg("dom"),
         py::arg("qi"), py::arg("interior"), py::arg("compute_region"), py::arg("exteriors"),
         py::arg("extend_vec") = 2);

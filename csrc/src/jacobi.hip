@@ -14,7 +14,16 @@
 //   - pure-vector full-rect launches (tail lanes cost 10%) with
 //     address-based 16 B alignment,
 //   - linearized scalar kernel for thin exterior slabs (any shape stays
-//     coalesced), grid-stride with a capped grid.
+//     coalesced), grid-stride with a capped grid,
+//   - single-domain fully periodic runs (the bench shape): the whole-step
+//     graph is jacobi_kernel_v4_lds<ZC, true> alone. It reads periodic
+//     neighbours from the far side of the same buffer, so the per-step
+//     halo copy (copy_batch, 59 us for 13.5 MB of strided faces) and the
+//     in-graph table swap (4 us) are gone; the kernel itself costs 8 us
+//     more (698 vs 689 us at 750^3). 0.714 vs 0.774 ms/step, median of 5
+//     alternating runs (profiles/README.md). Halos are stale after steps
+//     on this path until the next exchange(). STENCIL_JAC_WRAP=0 restores
+//     the translate graph.
 // Hot/cold sphere sources match the reference's behavior (truncated-int
 // sqrtf distance, HOT=1/COLD=0 fixed cells) so results are comparable.
 #include <hip/hip_runtime.h>
@@ -23,6 +32,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "stencil_amd/device_util.hpp"
@@ -50,6 +60,14 @@ struct JacobiParams {
   int32_t vecAll; // 1 = pure-vector launch (see launch_jacobi_on)
   // whole compute region (for the hot/cold spheres)
   int64_t cLoX, cLoY, cLoZ, cHiX, cHiY, cHiZ;
+};
+
+// kernargs of the WRAP instantiation of jacobi_kernel_v4_lds: the true x
+// region, before the vecAll row extension moved loX/extX. A struct of its
+// own, so the other kernels' kernarg layout (and code) stays as it was.
+struct JacobiWrapParams : JacobiParams {
+  int64_t trueLoX;
+  int32_t trueExtX;
 };
 
 __device__ __forceinline__ bool sphere_override(int64_t x, int64_t y, int64_t z,
@@ -203,8 +221,33 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4(JacobiParams p) {
 // (examples/jacobi_probe.cpp full-ldsrows). Requires blockDim (64,4,1)
 // and a vecAll launch (no scalar lanes; every lane's row exists because
 // the region is the interior rect of a radius>=1 domain).
-template <int ZC>
-__global__ void __launch_bounds__(256) jacobi_kernel_v4_lds(JacobiParams p) {
+//
+// WRAP = true (single-domain fully periodic whole-step graph, see
+// jacobi_graph_create): the region is the whole domain and periodic on all
+// three axes, so every neighbour outside [lo, lo+ext) is read from the far
+// end of the same buffer instead of from a halo cell. No halo is read, so
+// none has to be filled before the step. z: the -z plane of plane 0 is
+// plane extZ-1 and the +z plane of plane extZ-1 is plane 0 (uniform per
+// block / per iteration). y: the row staged below row 0 is row extY-1, the
+// row staged above row extY-1 is row 0 (uniform per block; lanes past extY
+// stage row 0, because the valid lane below reads their row as its +y
+// neighbour). x: the vecAll extension puts the true first cell at
+// component `under` of a row's first vector and the true last cell at
+// component 3-`over` of its last vector; the first lane loads `left` from
+// the row's last true cell, the last lane loads `right` from its first, and
+// a per-lane select feeds that scalar to the one component whose in-vector
+// neighbour is an overshoot cell. Overshoot components still compute and
+// store garbage into halo / pitch-slack bytes, which nothing on this path
+// reads.
+// gfx950 resource usage (-Rpass-analysis=kernel-resource-usage), the same
+// for ZC = 16 and 32:
+//   WRAP=false: 58 VGPRs, 54 SGPRs, 0 scratch, 8 waves/SIMD, 12288 B LDS
+//   WRAP=true : 58 VGPRs, 58 SGPRs, 0 scratch, 8 waves/SIMD, 12288 B LDS
+// (the row/plane selects and the six x-select lane masks live in scalar
+// registers; the WRAP=false instruction stream is unchanged by the flag)
+template <int ZC, bool WRAP = false>
+__global__ void __launch_bounds__(256)
+jacobi_kernel_v4_lds(std::conditional_t<WRAP, JacobiWrapParams, JacobiParams> p) {
   __shared__ float4 tile[2][6][64];
   const int32_t tx = threadIdx.x;
   const int32_t ry = threadIdx.y;
@@ -217,12 +260,29 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4_lds(JacobiParams p) {
   const int32_t u = min(u0, body4 - 1);
   // clamp to extY (the +y halo row, which exists for radius >= 1): a
   // VALID lane ry-1 reads lane ry's staged row as its +y neighbor, so
-  // lanes at ly0 == extY must stage the TRUE halo row, not a duplicate
-  const int32_t ly = min(ly0, (int32_t)p.extY);
-  // +y halo row staged by ry==3: one past its own row, clamped in-bounds
-  const int64_t pyHalo = (ly < p.extY) ? p.pitch : 0;
+  // lanes at ly0 == extY must stage the TRUE halo row, not a duplicate.
+  // WRAP: that neighbour is row 0.
+  const int32_t ly = WRAP ? (ly0 < p.extY ? ly0 : 0) : min(ly0, (int32_t)p.extY);
   const int32_t lz0 = blockIdx.z * ZC;
   const int32_t zEnd = min((int32_t)(lz0 + ZC), p.extZ);
+  // byte offsets from a lane's own cell to the rows/planes it stages:
+  //   myHalo: -y row staged by ry==0      pyHalo: +y row staged by ry==3
+  //   mzOff : the initial -z plane        (+z plane: colP, in the loop)
+  int64_t myHalo = 0, pyHalo, mzOff = 0;
+  if constexpr (WRAP) {
+    // all three depend on blockIdx only: scalar registers
+    const int32_t by0 = blockIdx.y * 4, by3 = by0 + 3;
+    const int64_t ySpan = (int64_t)(p.extY - 1) * p.pitch;
+    myHalo = by0 == 0 ? ySpan : -p.pitch;
+    // ry==3 at the last row wraps down to row 0; past it the lane already
+    // sits on row 0 and any in-range row will do
+    pyHalo = by3 < p.extY - 1 ? p.pitch : (by3 == p.extY - 1 ? -ySpan : 0);
+    mzOff = lz0 == 0 ? (int64_t)(p.extZ - 1) * p.plane : -p.plane;
+  } else {
+    // +y halo row staged by ry==3: one past its own row, clamped in-bounds
+    // (the -y row and -z plane are the fixed - p.pitch / - p.plane)
+    pyHalo = (ly < p.extY) ? p.pitch : 0;
+  }
 
   const int64_t gy = p.loY + ly;
   const int64_t ay = gy - p.allocY;
@@ -251,24 +311,71 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4_lds(JacobiParams p) {
     }
   };
 
-  float4 cm = *(const float4 *)(col - p.plane);
-  float4 cc = *(const float4 *)(col);
-  tile[0][ry + 1][tx] = cc;
-  if (ry == 0) tile[0][0][tx] = *(const float4 *)(col - p.pitch);
+  // WRAP x axis: where the first / last lane of a row find the periodic
+  // neighbour of the row's true end cells, and which component takes it
+  int32_t leftOff = -4, rightOff = 16;
+  bool wl1 = false, wl2 = false, wl3 = false; // left -> -x of component k
+  bool wr0 = false, wr1 = false, wr2 = false; // right -> +x of component k
+  if constexpr (WRAP) {
+    const int32_t under = (int32_t)(p.trueLoX - p.loX); // 0..3
+    const int32_t last = under + p.trueExtX - 1;        // in vector body4-1
+    const int32_t lastC = last & 3;                     // 3 - over
+    const bool first = u == 0, lastLane = u == body4 - 1;
+    if (first) leftOff = last * 4;                // row start + last
+    if (lastLane) rightOff = (under - 4 * u) * 4; // row start + under
+    wl1 = first && under == 1;
+    wl2 = first && under == 2;
+    wl3 = first && under == 3;
+    wr0 = lastLane && lastC == 0;
+    wr1 = lastLane && lastC == 1;
+    wr2 = lastLane && lastC == 2;
+  }
+
+  float4 cm, cc;
+  if constexpr (WRAP) {
+    cm = *(const float4 *)(col + mzOff);
+    cc = *(const float4 *)(col);
+    tile[0][ry + 1][tx] = cc;
+    if (ry == 0) tile[0][0][tx] = *(const float4 *)(col + myHalo);
+  } else {
+    cm = *(const float4 *)(col - p.plane);
+    cc = *(const float4 *)(col);
+    tile[0][ry + 1][tx] = cc;
+    if (ry == 0) tile[0][0][tx] = *(const float4 *)(col - p.pitch);
+  }
   if (ry == 3) tile[0][5][tx] = *(const float4 *)(col + pyHalo);
   __syncthreads();
   int buf = 0;
   for (int32_t lz = lz0; lz < zEnd; ++lz) {
-    const float4 cp = *(const float4 *)(col + p.plane);
-    const float left = *(const float *)(col - 4);
-    const float right = *(const float *)(col + 16);
+    // +z plane and the -y row in it; WRAP: uniform per iteration
+    const char *colP, *colPmy;
+    float left, right;
+    if constexpr (WRAP) {
+      colP = col + (lz == p.extZ - 1 ? -(int64_t)(p.extZ - 1) * p.plane : p.plane);
+      colPmy = colP + myHalo;
+      left = *(const float *)(col + leftOff);
+      right = *(const float *)(col + rightOff);
+    } else {
+      colP = col + p.plane;
+      colPmy = col + p.plane - p.pitch;
+      left = *(const float *)(col - 4);
+      right = *(const float *)(col + 16);
+    }
+    const float4 cp = *(const float4 *)colP;
     const float4 py = tile[buf][ry + 2][tx];
     const float4 my = tile[buf][ry][tx];
     float4 out;
-    out.x = (cc.y + left + py.x + my.x + cp.x + cm.x) / 6.0f;
-    out.y = (cc.z + cc.x + py.y + my.y + cp.y + cm.y) / 6.0f;
-    out.z = (cc.w + cc.y + py.z + my.z + cp.z + cm.z) / 6.0f;
-    out.w = (right + cc.z + py.w + my.w + cp.w + cm.w) / 6.0f;
+    if constexpr (WRAP) {
+      out.x = ((wr0 ? right : cc.y) + left + py.x + my.x + cp.x + cm.x) / 6.0f;
+      out.y = ((wr1 ? right : cc.z) + (wl1 ? left : cc.x) + py.y + my.y + cp.y + cm.y) / 6.0f;
+      out.z = ((wr2 ? right : cc.w) + (wl2 ? left : cc.y) + py.z + my.z + cp.z + cm.z) / 6.0f;
+      out.w = (right + (wl3 ? left : cc.z) + py.w + my.w + cp.w + cm.w) / 6.0f;
+    } else {
+      out.x = (cc.y + left + py.x + my.x + cp.x + cm.x) / 6.0f;
+      out.y = (cc.z + cc.x + py.y + my.y + cp.y + cm.y) / 6.0f;
+      out.z = (cc.w + cc.y + py.z + my.z + cp.z + cm.z) / 6.0f;
+      out.w = (right + cc.z + py.w + my.w + cp.w + cm.w) / 6.0f;
+    }
     sphere4((int32_t)(p.loZ + lz), out);
     if (valid) {
       typedef float vfloat4 __attribute__((ext_vector_type(4)));
@@ -276,8 +383,8 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4_lds(JacobiParams p) {
       __builtin_nontemporal_store(ov, (vfloat4 *)dcol);
     }
     tile[buf ^ 1][ry + 1][tx] = cp;
-    if (ry == 0) tile[buf ^ 1][0][tx] = *(const float4 *)(col + p.plane - p.pitch);
-    if (ry == 3) tile[buf ^ 1][5][tx] = *(const float4 *)(col + p.plane + pyHalo);
+    if (ry == 0) tile[buf ^ 1][0][tx] = *(const float4 *)colPmy;
+    if (ry == 3) tile[buf ^ 1][5][tx] = *(const float4 *)(colP + pyHalo);
     __syncthreads();
     buf ^= 1;
     cm = cc;
@@ -340,6 +447,16 @@ uint32_t grid_for(int64_t total, int block) {
 
 namespace {
 
+// STENCIL_JAC_LDS=0 turns the LDS-rows kernel off (read once)
+bool jac_use_lds() {
+  static int useLds = -1;
+  if (useLds < 0) {
+    const char *e = getenv("STENCIL_JAC_LDS");
+    useLds = (e && e[0] == '0') ? 0 : 1;
+  }
+  return useLds != 0;
+}
+
 // shared launch logic: builds params from the domain's CURRENT buffer
 // parity and enqueues the right kernel variant onto `stream`. Also used
 // by the whole-step hipGraph capture (pointers get baked per parity).
@@ -350,8 +467,13 @@ namespace {
 // no extension is allowed -- the fast path engages only when the region
 // is already aligned, which the allocation pad arranges for the overlap
 // interior).
+// wrap: launch the WRAP instantiation of jacobi_kernel_v4_lds (periodic
+// neighbours read in-kernel): the caller guarantees that `region` is the
+// whole domain and periodic on every axis (see jacobi_graph_create); throws
+// if the LDS kernel would not be selected.
 void launch_jacobi_on(LocalDomain &d, int64_t qi, const Rect3 &region,
-                      const Rect3 &computeRegion, hipStream_t stream, int fullRectVec = 0) {
+                      const Rect3 &computeRegion, hipStream_t stream, int fullRectVec = 0,
+                      bool wrap = false) {
   if (d.elem_size(qi) != 4) throw std::runtime_error("jacobi_step: quantity must be fp32");
   Vec3 ext = region.extent();
   if (ext.flatten() <= 0) return;
@@ -397,11 +519,9 @@ void launch_jacobi_on(LocalDomain &d, int64_t qi, const Rect3 &region,
       ext.x = e2;
     }
   }
-  static int useLds = -1;
-  if (useLds < 0) {
-    const char *e = getenv("STENCIL_JAC_LDS");
-    useLds = (e && e[0] == '0') ? 0 : 1;
-  }
+  const bool useLds = jac_use_lds();
+  if (wrap && !(p.vecAll && useLds))
+    throw std::runtime_error("jacobi: wrap launch needs the vecAll LDS kernel");
   if (p.vecAll && useLds && ext.x >= 8) {
     // LDS-staged y-rows variant (fixed 64x4 block); see jacobi_kernel_v4_lds
     static int zc = 0;
@@ -412,7 +532,16 @@ void launch_jacobi_on(LocalDomain &d, int64_t qi, const Rect3 &region,
     dim3 block(64, 4, 1);
     dim3 grid((uint32_t)((p.extX / 4 + 63) / 64), (uint32_t)((ext.y + 3) / 4),
               (uint32_t)((ext.z + zc - 1) / zc));
-    if (zc == 32)
+    if (wrap) {
+      JacobiWrapParams wp{};
+      static_cast<JacobiParams &>(wp) = p;
+      wp.trueLoX = region.lo.x;
+      wp.trueExtX = (int32_t)region.extent().x;
+      if (zc == 32)
+        hipLaunchKernelGGL((jacobi_kernel_v4_lds<32, true>), grid, block, 0, stream, wp);
+      else
+        hipLaunchKernelGGL((jacobi_kernel_v4_lds<16, true>), grid, block, 0, stream, wp);
+    } else if (zc == 32)
       hipLaunchKernelGGL(jacobi_kernel_v4_lds<32>, grid, block, 0, stream, p);
     else
       hipLaunchKernelGGL(jacobi_kernel_v4_lds<16>, grid, block, 0, stream, p);
@@ -470,8 +599,27 @@ struct StepGraph {
   int parity = 0;
   ExchangeEngine *eng = nullptr;
   int dom = 0;
+  // wrap graph: the stencil kernel alone; the device tables are flipped
+  // by jacobi_graph_launch, not by a graph node
+  bool wrap = false;
 };
 std::vector<std::unique_ptr<StepGraph>> g_stepGraphs;
+
+// The wrap-reading graph serves exactly the single-domain fully periodic
+// whole-domain step that launch_jacobi_on would give to
+// jacobi_kernel_v4_lds. STENCIL_JAC_WRAP=0 forces the translate graph (the
+// A/B lever and the fallback); it is read at each graph creation, which is
+// set-up and never on the step path.
+bool jacobi_wrap_eligible(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                          const Rect3 &computeRegion) {
+  const char *e = getenv("STENCIL_JAC_WRAP");
+  if (e && e[0] == '0') return false;
+  if (dom != 0 || !eng.self_wrap_only(qi, 0)) return false;
+  const LocalDomain &d = eng.domain(dom);
+  if (d.elem_size(qi) != 4) return false;
+  if (!(region == d.compute_region()) || !(region == computeRegion)) return false;
+  return region.extent().x >= 8 && jac_use_lds();
+}
 
 } // namespace
 
@@ -483,22 +631,37 @@ int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect
   // orchestration measured per step at 750^3 (exchange + launches +
   // stream syncs + swap upload). Single-process single-domain only (the
   // periodic self-wrap bench shape): no wire/IPC machinery may exist.
+  //
+  // Fully periodic single domain (jacobi_wrap_eligible): every halo cell
+  // is a copy of an interior cell of the same buffer, so the graph is the
+  // WRAP stencil kernel ALONE -- it reads the wrapped neighbour itself, no
+  // translate fills a halo (59 us/step of strided face copies at 750^3)
+  // and nothing in the graph reads the device pointer tables, so the
+  // table swap leaves the graph too (jacobi_graph_launch hoists it).
+  // Halos are STALE after steps taken on this path until the next
+  // exchange(); interior cells are exact.
   LocalDomain &d = eng.domain(dom);
   STENCIL_HIP(hipSetDevice(d.gpu()));
   auto sg = std::make_unique<StepGraph>();
   sg->eng = &eng;
   sg->dom = dom;
+  sg->wrap = jacobi_wrap_eligible(eng, dom, qi, region, computeRegion);
   STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking));
   for (int par = 0; par < 2; ++par) {
     STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-    eng.launch_translates_plain_on((uintptr_t)sg->stream, 0);
-    // physical boundaries (no-op on a fully periodic domain): the fill
-    // reads halos the translates delivered, same stream so ordered
-    eng.launch_boundary_plain_on((uintptr_t)sg->stream, 0);
-    // the graph's region is the whole interior rect: pure-vector launch
-    // (scalar tail lanes measured ~10% of the kernel in the probe)
-    launch_jacobi_on(d, qi, region, computeRegion, sg->stream, /*fullRectVec=*/1);
-    d.enqueue_table_swap(sg->stream);
+    if (sg->wrap) {
+      launch_jacobi_on(d, qi, region, computeRegion, sg->stream, /*fullRectVec=*/1,
+                       /*wrap=*/true);
+    } else {
+      eng.launch_translates_plain_on((uintptr_t)sg->stream, 0);
+      // physical boundaries (no-op on a fully periodic domain): the fill
+      // reads halos the translates delivered, same stream so ordered
+      eng.launch_boundary_plain_on((uintptr_t)sg->stream, 0);
+      // the graph's region is the whole interior rect: pure-vector launch
+      // (scalar tail lanes measured ~10% of the kernel in the probe)
+      launch_jacobi_on(d, qi, region, computeRegion, sg->stream, /*fullRectVec=*/1);
+      d.enqueue_table_swap(sg->stream);
+    }
     hipGraph_t g = nullptr;
     STENCIL_HIP(hipStreamEndCapture(sg->stream, &g));
     STENCIL_HIP(hipGraphInstantiate(&sg->exec[par], g, nullptr, nullptr, 0));
@@ -567,7 +730,13 @@ void jacobi_graph_launch(int64_t handle, int64_t nSteps) {
     sg.parity ^= 1;
     d.swap_host_only(); // in-graph kernel flips the device tables
   }
+  // the wrap graph has no swap node (nothing in it reads the tables): an
+  // even number of flips cancels, an odd one is ONE flip, enqueued behind
+  // the replays so host and device state agree in stream order on return
+  if (sg.wrap && (nSteps & 1)) d.enqueue_table_swap(sg.stream);
 }
+
+bool jacobi_graph_is_wrap(int64_t handle) { return g_stepGraphs.at(handle)->wrap; }
 
 void jacobi_graph_sync(int64_t handle) {
   StepGraph &sg = *g_stepGraphs.at(handle);

@@ -88,6 +88,16 @@ class Jacobi3D:
         # removing ~0.25 ms/step of host orchestration at 750^3. Overlap
         # was measured a wash against serial at this shape (gpu20b), so
         # the serial capture loses nothing.
+        # When every axis is periodic the graph is the stencil kernel
+        # ALONE: it reads the wrapped neighbour from the far side of the
+        # buffer, so no translate fills a halo and the table swap moves
+        # out of the graph (one swap after an odd run(n); see
+        # csrc/src/jacobi.hip jacobi_graph_create; STENCIL_JAC_WRAP=0
+        # restores the translate graph). Halos are then STALE after
+        # step()/run() until the next dd.exchange(): read_global over a
+        # region that includes halo cells shows old values there. With a
+        # non-periodic face the graph is [translate -> boundary fill ->
+        # jacobi -> swap] as before.
         import os
 
         self._graph = None
