@@ -57,6 +57,29 @@ void jacobi_mr_graph_pre(int64_t handle);
 void jacobi_mr_graph_post(int64_t handle);
 void jacobi_mr_graph_sync(int64_t handle);
 
+// Generic constant-coefficient linear stencil (csrc/src/stencil_op.hip):
+//   next[dstQ](p) = sum_k weights[k] * curr[srcQ](p + offsets[k])
+// for every p in `region` (global coords), on compute_stream(dom, streamId).
+// srcQ == dstQ is allowed (reads curr, writes next). Accumulation is in the
+// quantity's own type; weights are rounded to it once, at launch; the
+// summation order is unspecified. Unlike jacobi_step's row extension this
+// writes NOTHING outside `region` (no halo cell, no pitch slack, no other
+// quantity) and reads no cell outside the rows of region (+) offsets, so
+// it is safe next to OPEN boundaries, IPC peers and asymmetric radii.
+// Star stencils (every tap on an axis) of radius <= 4 over regions at
+// least 8 cells wide run the 16 B-strip z-marching kernel; everything else
+// runs the linearised tap-table kernel.
+// Throws std::invalid_argument when the quantities' element size does not
+// match `type`, when region (+) offsets leaves full_region(), or when
+// there are 0 or more than 128 taps. An empty region is a no-op.
+struct StencilTaps {
+  std::vector<Vec3> offsets;
+  std::vector<double> weights;
+};
+enum class StencilType { F32, F64 };
+void stencil_apply(ExchangeEngine &eng, int dom, int64_t srcQ, int64_t dstQ, const Rect3 &region,
+                   const StencilTaps &taps, StencilType type, int streamId = 0);
+
 // physical coefficients of the MHD solver (see csrc/src/mhd.hip)
 struct MhdCoeffs {
   double dsx = 1.0, dsy = 1.0, dsz = 1.0;

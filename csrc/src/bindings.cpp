@@ -311,6 +311,28 @@ PYBIND11_MODULE(_C, m) {
         py::arg("region"), py::arg("compute_region"), py::arg("stream_id") = 0,
         py::arg("extend_vec") = 0);
   m.def("fill_f32", &fill_f32);
+
+  // generic weighted stencil (csrc/src/stencil_op.hip)
+  py::class_<StencilTaps>(m, "StencilTaps")
+      .def(py::init<>())
+      .def_readwrite("offsets", &StencilTaps::offsets)
+      .def_readwrite("weights", &StencilTaps::weights);
+  py::enum_<StencilType>(m, "StencilType")
+      .value("F32", StencilType::F32)
+      .value("F64", StencilType::F64);
+  m.def(
+      "stencil_apply",
+      [](ExchangeEngine &eng, int dom, int64_t srcQ, int64_t dstQ, const Rect3 &region,
+         const StencilTaps &taps, StencilType type, int streamId) {
+        try {
+          stencil_apply(eng, dom, srcQ, dstQ, region, taps, type, streamId);
+        } catch (const std::invalid_argument &e) {
+          throw py::value_error(e.what());
+        }
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("src_q"), py::arg("dst_q"), py::arg("region"),
+      py::arg("taps"), py::arg("type"), py::arg("stream_id") = 0);
+
   m.def("jacobi_graph_create", &jacobi_graph_create, py::arg("eng"), py::arg("dom"),
         py::arg("qi"), py::arg("region"), py::arg("compute_region"));
   m.def("jacobi_graph_create_overlap", &jacobi_graph_create_overlap, py::arg("eng"),

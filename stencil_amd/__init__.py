@@ -52,6 +52,7 @@ from .boundary import Boundary
 from .core import DataHandle, DistributedDomain, Method
 from .parallel.machine import Machine
 from .parallel.placement import PlacementStrategy
+from .stencil import Stencil
 
 __all__ = [
     "Machine",
@@ -62,6 +63,7 @@ __all__ = [
     "PlacementStrategy",
     "Radius",
     "Rect3",
+    "Stencil",
     "Vec3",
     "prime_factors",
     "_C",

@@ -337,6 +337,67 @@ class DistributedDomain:
         self.backend.swap()
         self.time_swap += time.perf_counter() - t0
 
+    # ---- generic stencil operator ----
+    def _stencil_dtype(self, src: DataHandle, dst: DataHandle) -> np.dtype:
+        if src.dtype != dst.dtype:
+            raise ValueError(f"apply_stencil: src is {src.dtype} but dst is {dst.dtype}")
+        if src.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"apply_stencil supports float32/float64 quantities, got {src.dtype}")
+        return src.dtype
+
+    def apply_stencil(self, stencil, src: DataHandle, dst: Optional[DataHandle] = None,
+                      where="all", stream_id: Optional[int] = None):
+        """next[dst] = stencil(curr[src]) on every local domain (dst=None:
+        the same quantity; the kernel reads curr and writes next, so that
+        is safe). `where` selects the cells: "all" (local_rect),
+        "interior" (get_interior: cells whose taps read no halo),
+        "exterior" (get_exterior slabs) or an explicit global box (lo, hi),
+        which is applied as given on every local domain: it must lie inside
+        each one's allocation together with the taps. Work is enqueued on compute
+        stream `stream_id` (default: 1 for exterior slabs, 0 otherwise);
+        call backend.sync_compute() before reading. The halos the stencil
+        reads must be current (exchange()) except for where="interior".
+        float32/float64 quantities only (ValueError otherwise, also for
+        taps that reach outside the allocated halo)."""
+        dst = src if dst is None else dst
+        dt = self._stencil_dtype(src, dst)
+        if isinstance(where, str):
+            if where not in ("all", "interior", "exterior"):
+                raise ValueError(f"apply_stencil: where={where!r}")
+            if where == "all":
+                boxes = [[self.local_rect(li)] for li in range(self.num_local())]
+            elif where == "interior":
+                boxes = [[b] for b in self.get_interior()]
+            else:
+                boxes = self.get_exterior()
+            sid = (1 if where == "exterior" else 0) if stream_id is None else stream_id
+        else:
+            lo, hi = where
+            boxes = [[(tuple(lo), tuple(hi))] for _ in range(self.num_local())]
+            sid = 0 if stream_id is None else stream_id
+        for li, bs in enumerate(boxes):
+            for lo, hi in bs:
+                self.backend.stencil_apply(li, src.index, dst.index, lo, hi, stencil, dt, sid)
+
+    def step_stencil(self, stencil, src: DataHandle, dst: Optional[DataHandle] = None,
+                     overlap: bool = True):
+        """one time step of a stencil update: overlap=True computes the
+        interior while the halos move, then the exterior slabs (interior,
+        exchange(), exterior, sync_compute, swap()); overlap=False is
+        exchange, all, sync, swap. The domain's radius must cover the
+        stencil (set_radius(stencil.radius()) is the minimal choice).
+        Always eager: whole-step hipGraphs for this operator are out of
+        scope (Jacobi3D has them for its fixed 7-point kernel)."""
+        if overlap:
+            self.apply_stencil(stencil, src, dst, where="interior")
+            self.exchange()
+            self.apply_stencil(stencil, src, dst, where="exterior")
+        else:
+            self.exchange()
+            self.apply_stencil(stencil, src, dst, where="all")
+        self.backend.sync_compute()
+        self.swap()
+
     # ---- geometry queries ----
     def any_methods(self, m: Method) -> bool:
         """True if any of the given transport methods are enabled

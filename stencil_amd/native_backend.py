@@ -71,6 +71,7 @@ class NativeBackend:
         self._has_boundary = [False] * ng
         self.boundary_bytes = 0  # bytes one full boundary fill writes
         self.boundary_lines: List[str] = []  # plan-file lines
+        self._stencil_taps = {}  # id(Stencil) -> (Stencil, _C.StencilTaps): built once
 
     # ---- plan registration ----
     def register_plan(self, plan: ExchangePlan, ctx: Optional[dict] = None):
@@ -675,6 +676,27 @@ class NativeBackend:
                     c_lo: Vec, c_hi: Vec, stream_id: int = 0, extend_vec: bool = False):
         _C.jacobi_step(self.engine, li, qi, _rect3(region_lo, region_hi), _rect3(c_lo, c_hi),
                        stream_id, extend_vec)
+
+    def stencil_apply(self, li: int, src_qi: int, dst_qi: int, lo: Vec, hi: Vec, stencil,
+                      dtype, stream_id: int = 0):
+        """next[dst_qi] = stencil(curr[src_qi]) over the global box [lo, hi)
+        (csrc/src/stencil_op.hip); dtype is float32 or float64. Raises
+        ValueError on a dtype/element-size mismatch or a tap that reads
+        outside the allocation; nothing is launched then."""
+        import numpy as np
+
+        dt = np.dtype(dtype)
+        if dt == np.float32:
+            ty = _C.StencilType.F32
+        elif dt == np.float64:
+            ty = _C.StencilType.F64
+        else:
+            raise ValueError(f"stencil_apply supports float32/float64, got {dt}")
+        taps = self._stencil_taps.get(id(stencil))
+        if taps is None or taps[0] is not stencil:
+            taps = (stencil, stencil.to_native())
+            self._stencil_taps[id(stencil)] = taps
+        _C.stencil_apply(self.engine, li, src_qi, dst_qi, _rect3(lo, hi), taps[1], ty, stream_id)
 
     def jacobi_graph_create(self, li: int, qi: int, region_lo: Vec, region_hi: Vec,
                             c_lo: Vec, c_hi: Vec) -> int:

@@ -6,27 +6,35 @@ stream of the given ExchangeEngine; regions are global-coordinate Rect3s.
   (csrc/src/jacobi.hip, z-marching float4 kernel)
 - mhd_div_pass / mhd_substep: separable-derivative 6th-order MHD
   (csrc/src/mhd.hip)
+- stencil_apply: generic weighted stencil described by a tap table
+  (csrc/src/stencil_op.hip; StencilTaps / StencilType are its arguments)
 - fill_f32 / init_harmonic_f64: field initialization (csrc/src/init.hip)
 - field_stats: min/max/RMS reduction (csrc/src/reductions.hip)
 """
 from .._C import (  # noqa: F401
     FieldStats,
     MhdCoeffs,
+    StencilTaps,
+    StencilType,
     field_stats,
     fill_f32,
     init_harmonic_f64,
     jacobi_step,
     mhd_div_pass,
     mhd_substep,
+    stencil_apply,
 )
 
 __all__ = [
     "FieldStats",
     "MhdCoeffs",
+    "StencilTaps",
+    "StencilType",
     "field_stats",
     "fill_f32",
     "init_harmonic_f64",
     "jacobi_step",
     "mhd_div_pass",
     "mhd_substep",
+    "stencil_apply",
 ]

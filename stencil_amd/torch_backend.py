@@ -302,5 +302,46 @@ class TorchBackend:
         out = torch.where(mask(cold), torch.zeros_like(avg), out)
         dom.next[qi][sl] = out
 
+    def stencil_apply(self, li, src_qi, dst_qi, lo, hi, stencil, dtype, stream_id=0):
+        """slicing reference of the native stencil_apply: next[dst_qi] =
+        sum_k w_k * curr[src_qi] shifted by o_k over the global box [lo, hi),
+        accumulated in the quantity's type with weights rounded to it once.
+        Same validation as the native op (ValueError)."""
+        import numpy as np
+
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"stencil_apply supports float32/float64, got {dt}")
+        dom = self.domains[li]
+        for qi in (src_qi, dst_qi):
+            if not 0 <= qi < len(dom.elem_sizes):
+                raise ValueError("stencil_apply: no such quantity")
+            if dom.elem_sizes[qi] != dt.itemsize:
+                raise ValueError(
+                    "stencil_apply: element size of the quantities does not match the stencil type"
+                )
+        offsets, weights = stencil.offsets, stencil.weights
+        if not 1 <= len(offsets) <= 128:
+            raise ValueError(f"stencil_apply: want 1..128 taps, got {len(offsets)}")
+        ext = tuple(hi[i] - lo[i] for i in range(3))
+        if min(ext) <= 0:
+            return
+        flo = dom.full_lo()
+        raw = dom.raw_size()
+        pos = tuple(lo[i] - flo[i] for i in range(3))
+        for o in [(0, 0, 0)] + offsets:
+            for i in range(3):
+                if pos[i] + o[i] < 0 or pos[i] + o[i] + ext[i] > raw[i]:
+                    raise ValueError(
+                        f"stencil_apply: tap {o} over region {lo}..{hi} reads outside the allocation"
+                    )
+        src = dom.curr[src_qi]
+        tdt = src.dtype
+        acc = torch.zeros((ext[2], ext[1], ext[0]), dtype=tdt, device=src.device)
+        for o, w in zip(offsets, weights):
+            p = (pos[0] + o[0], pos[1] + o[1], pos[2] + o[2])
+            acc += torch.tensor(w, dtype=tdt, device=src.device) * src[dom._sl(p, ext)]
+        dom.next[dst_qi][dom._sl(pos, ext)] = acc
+
     def sync_compute(self):
         pass
