@@ -35,11 +35,6 @@ void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, flo
 // jacobi_graph_is_wrap() tells which graph a handle holds.
 int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
                             const Rect3 &computeRegion);
-// overlap variant: translate forked concurrent with the interior kernel
-// inside the graph (STENCIL_AMD_GRAPH_OVERLAP=1; see csrc/src/jacobi.hip)
-int64_t jacobi_graph_create_overlap(ExchangeEngine &eng, int dom, int64_t qi,
-                                    const Rect3 &interior, const Rect3 &computeRegion,
-                                    const std::vector<Rect3> &exteriors);
 void jacobi_graph_launch(int64_t handle, int64_t nSteps);
 void jacobi_graph_sync(int64_t handle);
 bool jacobi_graph_is_wrap(int64_t handle);

@@ -85,9 +85,9 @@ class Jacobi3D:
         # whole-step hipGraph fast path: the single-process single-domain
         # periodic self-wrap shape (the N=1 bench) replays a captured
         # [translate -> jacobi -> device table swap] graph per step,
-        # removing ~0.25 ms/step of host orchestration at 750^3. Overlap
-        # was measured a wash against serial at this shape (gpu20b), so
-        # the serial capture loses nothing.
+        # removing ~0.25 ms/step of host orchestration at 750^3. The
+        # capture is serial: overlap measured no better at this shape
+        # (docs/DESIGN.md).
         # When every axis is periodic the graph is the stencil kernel
         # ALONE: it reads the wrapped neighbour from the far side of the
         # buffer, so no translate fills a halo and the table swap moves
@@ -112,23 +112,10 @@ class Jacobi3D:
             and graphs_on
             and not staged_local
         ):
-            from .. import _C
-
             lo, hi = self.dd.local_rect(0)
-            if os.environ.get("STENCIL_AMD_GRAPH_OVERLAP", "0") == "1":
-                # experiment: translate forked || interior inside the graph
-                ilo, ihi = self.interiors[0]
-                self._graph = _C.jacobi_graph_create_overlap(
-                    self.dd.backend.engine, 0, self.h.index,
-                    _C.Rect3(_C.Vec3(*ilo), _C.Vec3(*ihi)),
-                    _C.Rect3(_C.Vec3(*self.compute_lo), _C.Vec3(*self.compute_hi)),
-                    [_C.Rect3(_C.Vec3(*blo), _C.Vec3(*bhi))
-                     for blo, bhi in self.exteriors[0]],
-                )
-            else:
-                self._graph = self.dd.backend.jacobi_graph_create(
-                    0, self.h.index, lo, hi, self.compute_lo, self.compute_hi
-                )
+            self._graph = self.dd.backend.jacobi_graph_create(
+                0, self.h.index, lo, hi, self.compute_lo, self.compute_hi
+            )
         elif (
             self.m == 1
             and self.dd.backend_kind == "native"

@@ -49,6 +49,39 @@ def test_mhd_matches_numpy_reference(n_domains):
             np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12, err_msg=f"{name} li={li}")
 
 
+@pytest.mark.parametrize("mode", ["graph", "eager"])
+def test_mhd_ychunk_dispatch_matches_numpy_reference(mode, monkeypatch):
+    """y-chunked block dispatch (the default at every benchmark size): with
+    the default 64x2x2 block, (16, 68, 12) gives a 1x34x6 block grid, for
+    which the default chunk request of 32 picks C = 17, so the in-kernel
+    remap really runs. x does not fill a block and the three extents differ,
+    so an axis mix-up in the block decode cannot cancel."""
+    monkeypatch.setenv("STENCIL_AMD_STEP_GRAPH", "1" if mode == "graph" else "0")
+    size = (16, 68, 12)
+    app = Astaroth(size, backend="native", gpus=[0])
+    app.realize()
+    if mode == "graph":
+        assert app._graph is not None, "mhd graph did not activate"
+    else:
+        assert app._graph is None
+    app.init_fields()
+
+    cf = {k: float(app.conf[k]) for k in ("dsx", "dsy", "dsz", "cs2", "cp_inv", "nu", "eta", "chi")}
+    curr = global_init(size)
+    nxt = [np.zeros(curr[0].shape) for _ in range(8)]
+    dt = 1e-4
+    for _ in range(2):  # two full iterations = 6 substeps
+        app.step(dt=dt)
+        for s in range(3):
+            curr, nxt = M.substep(curr, nxt, s, dt, cf)
+
+    lo, hi = app.dd.local_rect(0)
+    for qi, name in enumerate(FIELDS):
+        got = app.read_field(0, name)
+        want = curr[qi][lo[2] : hi[2], lo[1] : hi[1], lo[0] : hi[0]]
+        np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-12, err_msg=name)
+
+
 def test_mhd_no_compute_mode():
     app = Astaroth((16, 16, 16), backend="native", gpus=[0])
     app.realize()
@@ -56,6 +89,20 @@ def test_mhd_no_compute_mode():
     app.step(compute=False)  # pure exchange path must run
     arr = app.read_field(0, "uux")
     assert np.isfinite(arr).all()
+
+
+@pytest.mark.parametrize("stream_id", [-1, 2])
+def test_mhd_rejects_stream_id_other_than_0_or_1(stream_id):
+    """an engine has compute streams 0 and 1 per domain; any other id is an
+    error, not an alias of one of them"""
+    from stencil_amd import _C
+
+    app = Astaroth((16, 16, 16), backend="native", gpus=[0])
+    app.realize()
+    lo, hi = app.dd.local_rect(0)
+    rect = _C.Rect3(_C.Vec3(*lo), _C.Vec3(*hi))
+    with pytest.raises(ValueError):
+        _C.mhd_div_pass(app.dd.backend.engine, 0, rect, app.cf, stream_id)
 
 
 def test_mhd_overlap_equals_no_overlap():
