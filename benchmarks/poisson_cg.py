@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Conjugate-gradient benchmark: (sigma I - laplacian) x = b on a size^3
+grid with Poisson3D, exactly --iters iterations (tol = 0).
+
+Prints one JSON line: ms_per_iter, gcells_per_s and the host wall time per
+iteration of the three phases (each ends in a host sync):
+  operator_ms  apply_stencil(A, p) + exchange of p
+  dot_ms       p . A p
+  update_ms    cg_update (x, r, r . r) + the p update
+--kernels N adds a kernel-only window per vector kernel (N launches
+enqueued, one sync) with its effective bandwidth, one element read or
+written counting as one pass: dot 2, cg_update 6, the p update 3; and the
+cost of one empty host sync of the compute stream.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
+
+import numpy as np
+
+import stencil_amd as sa
+from stencil_amd import Boundary
+from stencil_amd.models.poisson3d import Poisson3D
+
+_BOUNDARIES = {
+    "periodic": None,
+    "fixed": {"all": (Boundary.FIXED, 0)},
+    "mirror": {"all": (Boundary.MIRROR, 0)},
+    "antimirror": {"all": (Boundary.ANTIMIRROR, 0)},
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=256, help="edge of the global cube")
+    ap.add_argument("--order", type=int, default=2, choices=[2, 4, 6, 8])
+    ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
+    ap.add_argument("--sigma", type=float, default=1.0)
+    ap.add_argument("--boundary", default="periodic", choices=sorted(_BOUNDARIES))
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=3, help="iterations of an untimed first solve")
+    ap.add_argument("--backend", default="native", choices=["native", "torch"])
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--no-overlap", action="store_true")
+    ap.add_argument("--kernels", type=int, default=0, metavar="N",
+                    help="also time N back-to-back launches of each vector kernel")
+    args = ap.parse_args()
+
+    dtype = np.float32 if args.dtype == "f32" else np.float64
+    gpus = list(range(args.gpus)) if args.backend == "native" else [0] * args.gpus
+    size = (args.size,) * 3
+    app = Poisson3D(size, order=args.order, dtype=dtype, sigma=args.sigma, backend=args.backend,
+                    gpus=gpus, boundary=_BOUNDARIES[args.boundary])
+    app.realize()
+    dd = app.dd
+    rng = np.random.default_rng(0)
+    for li in range(dd.num_local()):
+        lo, hi = dd.local_rect(li)
+        shape = (hi[2] - lo[2], hi[1] - lo[1], hi[0] - lo[0])
+        dd.write_global(li, lo, rng.standard_normal(shape, dtype=np.float32).astype(dtype), app.b)
+
+    overlap = not args.no_overlap
+    if args.warmup:
+        app.solve(tol=0.0, max_iter=args.warmup, overlap=overlap)
+    dd.backend.sync()
+    t0 = time.perf_counter()
+    res = app.solve(tol=0.0, max_iter=args.iters, overlap=overlap)
+    dd.backend.sync()
+    dt = time.perf_counter() - t0
+    n = max(res.iterations, 1)
+    cells = size[0] * size[1] * size[2]
+    ms = dt / n * 1e3
+    ph = app.cg.phase_times
+    out = {
+        "benchmark": "poisson_cg",
+        "size": args.size,
+        "order": args.order,
+        "dtype": args.dtype,
+        "sigma": args.sigma,
+        "boundary": args.boundary,
+        "gpus": args.gpus,
+        "backend": args.backend,
+        "overlap": overlap,
+        "iters": res.iterations,
+        "reason": res.reason,
+        "final_residual": res.residuals[-1],
+        "ms_per_iter": ms,
+        "gcells_per_s": cells / ms / 1e6,
+        "operator_ms": ph["operator"] / n * 1e3,
+        "dot_ms": ph["dot"] / n * 1e3,
+        "update_ms": ph["update"] / n * 1e3,
+    }
+
+    if args.kernels:
+        k = args.kernels
+        es = np.dtype(dtype).itemsize
+        x, r, p = app.x, app.r, app.p
+
+        def window(fn):
+            fn()
+            dd.backend.sync()
+            t = time.perf_counter()
+            for _ in range(k):
+                fn()
+            dd.backend.sync()
+            return (time.perf_counter() - t) / k * 1e3
+
+        def report(name, passes, t_ms):
+            out[f"{name}_kernel_ms"] = t_ms
+            out[f"{name}_gb_per_s"] = passes * cells * es / t_ms / 1e6
+
+        report("axpby", 3, window(lambda: dd.axpby(1.0, r, 0.5, p, out=p)))
+        report("stencil", 2, window(lambda: dd.apply_stencil(app.stencil, p, where="all")))
+        # the reductions wait for their value: a window of k synchronous calls
+        report("dot", 2, window(lambda: dd.dot(p, sa.Next(p))))
+        report("cg_update", 6, window(lambda: dd.cg_update(1e-30, x, p, r)))
+        t = time.perf_counter()
+        for _ in range(k):
+            dd.backend.sync_compute()
+        out["empty_sync_ms"] = (time.perf_counter() - t) / k * 1e3
+        # the control-plane sum of the per-rank values (world 1: no collective)
+        t = time.perf_counter()
+        for _ in range(k):
+            dd._global_sum([1.0] * dd.num_local())
+        out["global_sum_ms"] = (time.perf_counter() - t) / k * 1e3
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

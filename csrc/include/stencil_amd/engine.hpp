@@ -249,6 +249,21 @@ public:
   LocalDomain &domain(int i) { return *domains_[i]; }
   int num_domains() const { return (int)domains_.size(); }
 
+  //// scratch of the field reductions (csrc/src/vector_ops.hip): per
+  //// domain, one device array of per-block partial sums and a pinned host
+  //// landing buffer of the same size, allocated on first use and freed
+  //// with the engine. One reduction per domain may be in flight.
+  static constexpr int kReducePartials = 4096; // the reductions' grid cap
+  struct ReduceScratch {
+    double *dev = nullptr;
+    double *host = nullptr;
+    hipStream_t stream = nullptr; // stream of the reduction in flight
+    int count = 0;                // its number of partials (0: empty region)
+    bool pending = false;
+  };
+  // allocate = false: the bookkeeping only (an empty region launches nothing)
+  ReduceScratch &reduce_scratch(int dom, bool allocate = true);
+
   // true when exchange group `group` is nothing but ONE domain's periodic
   // self-wrap of quantity qi on every axis: a single local domain, no
   // remote views, staging buffers, packs or boundary fills, and self
@@ -323,6 +338,7 @@ private:
   std::map<int, hipEvent_t> fenceEvents_;  // per device: pack->unpack fences
   std::vector<hipStream_t> computeStreams_;  // per domain, stream 0
   std::vector<hipStream_t> computeStreams2_; // per domain, stream 1
+  std::vector<ReduceScratch> reduce_;        // per domain
 
   // pack/unpack launch-group encoding for exchange-group g:
   //   wire = 3g, colo staging parity 0/1 = 3g+1 / 3g+2

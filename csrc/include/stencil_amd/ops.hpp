@@ -75,6 +75,48 @@ enum class StencilType { F32, F64 };
 void stencil_apply(ExchangeEngine &eng, int dom, int64_t srcQ, int64_t dstQ, const Rect3 &region,
                    const StencilTaps &taps, StencilType type, int streamId = 0);
 
+// Vector operations on pitched quantities (csrc/src/vector_ops.hip): the
+// building blocks of Krylov solvers. Every op works on a global-coordinate
+// `region` of one local domain, on float32 or float64 quantities (all
+// operands of one op of the same type), on compute_stream(dom, streamId).
+// An operand is (quantity index, nextBuf). Nothing outside `region` is
+// written in any buffer and no cell outside it enters the arithmetic.
+// Regions at least 8 cells wide whose operand rows are equally aligned run
+// on 16 B strips aligned by address with scalar head/tail lanes; the rest
+// runs linearised. All throw std::invalid_argument, and launch nothing,
+// for an unknown domain or quantity, an element size other than 4 or 8 or
+// one that differs between operands, and a region outside full_region().
+// An empty region is a no-op (reductions return 0).
+//
+// The reductions are deterministic: per-wave shuffles, per-block LDS, one
+// partial per block, partials summed in index order on the host; the same
+// input on the same launch shape gives the same bits. They use the
+// engine's per-domain scratch (no allocation per call) and block the host
+// once. With several local domains, call the *_begin form on each, then
+// reduction_end on each: one reduction per domain may be in flight.
+
+// sum over region of a(p) * b(p); products and sums in fp64
+double field_dot(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                 const Rect3 &region, int streamId = 0);
+void field_dot_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                     const Rect3 &region, int streamId = 0);
+// out = alpha * x + beta * y in the quantity's type (alpha, beta rounded to
+// it once at launch; FMA contraction unspecified). out may be the buffer
+// of x or of y: the op is element-wise.
+void field_axpby(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
+                 int64_t y, bool yNext, int64_t out, bool outNext, const Rect3 &region,
+                 int streamId = 0);
+// fused conjugate-gradient update, one pass instead of three:
+//   curr[x] += alpha * curr[p];  curr[r] -= alpha * next[p]
+// returning sum r_new^2 (fp64 accumulation of the rounded r_new). next[p]
+// is where stencil_apply(A, p, p) leaves A p. x, p and r are distinct.
+double cg_update(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
+                 const Rect3 &region, int streamId = 0);
+void cg_update_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
+                     const Rect3 &region, int streamId = 0);
+// wait for the reduction begun on `dom` and return its value
+double reduction_end(ExchangeEngine &eng, int dom);
+
 // physical coefficients of the MHD solver (see csrc/src/mhd.hip)
 struct MhdCoeffs {
   double dsx = 1.0, dsy = 1.0, dsz = 1.0;

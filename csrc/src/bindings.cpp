@@ -333,6 +333,73 @@ PYBIND11_MODULE(_C, m) {
       py::arg("eng"), py::arg("dom"), py::arg("src_q"), py::arg("dst_q"), py::arg("region"),
       py::arg("taps"), py::arg("type"), py::arg("stream_id") = 0);
 
+  // vector operations (csrc/src/vector_ops.hip); invalid arguments are ValueErrors
+  auto value_errors = [](auto &&call) {
+    try {
+      return call();
+    } catch (const std::invalid_argument &e) {
+      throw py::value_error(e.what());
+    }
+  };
+  m.def(
+      "field_dot",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                     const Rect3 &region, int streamId) {
+        return value_errors(
+            [&] { return field_dot(eng, dom, a, aNext, b, bNext, region, streamId); });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "field_dot_begin",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_dot_begin(eng, dom, a, aNext, b, bNext, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "field_axpby",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                     double beta, int64_t y, bool yNext, int64_t out, bool outNext,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_axpby(eng, dom, alpha, x, xNext, beta, y, yNext, out, outNext, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
+      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"), py::arg("out_next"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "cg_update",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
+                     const Rect3 &region, int streamId) {
+        return value_errors([&] { return cg_update(eng, dom, alpha, x, p, r, region, streamId); });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "cg_update_begin",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          cg_update_begin(eng, dom, alpha, x, p, r, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "reduction_end",
+      [value_errors](ExchangeEngine &eng, int dom) {
+        return value_errors([&] { return reduction_end(eng, dom); });
+      },
+      py::arg("eng"), py::arg("dom"));
+
   m.def("jacobi_graph_create", &jacobi_graph_create, py::arg("eng"), py::arg("dom"),
         py::arg("qi"), py::arg("region"), py::arg("compute_region"));
   m.def("jacobi_graph_launch", &jacobi_graph_launch, py::arg("handle"), py::arg("n_steps") = 1);

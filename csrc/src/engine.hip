@@ -179,6 +179,7 @@ ExchangeEngine::ExchangeEngine(std::vector<std::shared_ptr<LocalDomain>> domains
     : domains_(std::move(domains)) {
   computeStreams_.resize(domains_.size(), nullptr);
   computeStreams2_.resize(domains_.size(), nullptr);
+  reduce_.resize(domains_.size());
   // spin-wait host syncs: interrupt-based stream-sync wakeups cost
   // 20-100 us each on ROCm; an HPC bench prefers burning the core.
   // Tolerant: the flag may be rejected once a device context exists.
@@ -207,6 +208,10 @@ ExchangeEngine::~ExchangeEngine() {
   for (auto *vec : {&computeStreams_, &computeStreams2_})
     for (auto s : *vec)
       if (s) (void)hipStreamDestroy(s);
+  for (auto &r : reduce_) {
+    if (r.dev) (void)hipFree(r.dev);
+    if (r.host) (void)hipHostFree(r.host);
+  }
   for (auto &b : buffers_) {
     if (!b.ptr) continue;
     if (b.external) {
@@ -594,6 +599,16 @@ void ExchangeEngine::sync_packs() {
 void ExchangeEngine::sync_all() {
   sync_translates();
   sync_packs();
+}
+
+ExchangeEngine::ReduceScratch &ExchangeEngine::reduce_scratch(int dom, bool allocate) {
+  ReduceScratch &r = reduce_.at(dom);
+  if (allocate && !r.dev) {
+    STENCIL_HIP(hipSetDevice(domains_[dom]->gpu()));
+    STENCIL_HIP(hipMalloc((void **)&r.dev, kReducePartials * sizeof(double)));
+    STENCIL_HIP(hipHostMalloc((void **)&r.host, kReducePartials * sizeof(double), 0));
+  }
+  return r;
 }
 
 void ExchangeEngine::sync_compute() {

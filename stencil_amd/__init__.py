@@ -49,7 +49,7 @@ except ImportError as e:  # pragma: no cover
 
 from ._C import Radius, Rect3, Vec3, prime_factors
 from .boundary import Boundary
-from .core import DataHandle, DistributedDomain, Method
+from .core import DataHandle, DistributedDomain, Method, Next
 from .parallel.machine import Machine
 from .parallel.placement import PlacementStrategy
 from .stencil import Stencil
@@ -60,6 +60,7 @@ __all__ = [
     "Boundary",
     "DataHandle",
     "Method",
+    "Next",
     "PlacementStrategy",
     "Radius",
     "Rect3",

@@ -51,6 +51,18 @@ class DataHandle:
         self.dtype = np.dtype(dtype) if dtype is not None else np.dtype(_NP_DTYPES[elem_size])
 
 
+class Next:
+    """marks "the next buffer of this quantity" wherever a vector operation
+    (dot, axpby) expects an operand; a bare DataHandle means curr"""
+
+    __slots__ = ("handle",)
+
+    def __init__(self, handle: DataHandle):
+        if not isinstance(handle, DataHandle):
+            raise TypeError("Next() wraps a DataHandle")
+        self.handle = handle
+
+
 def _np_dtype_of(dtype_or_size) -> np.dtype:
     """resolve an add_data() spec (torch dtype / numpy dtype / element
     size) to the numpy dtype used for host views. Kept alongside the
@@ -397,6 +409,80 @@ class DistributedDomain:
             self.apply_stencil(stencil, src, dst, where="all")
         self.backend.sync_compute()
         self.swap()
+
+    # ---- vector operations (the building blocks of solvers/) ----
+    def _vector_operands(self, op: str, operands):
+        """[(quantity index, next_buf)] of handles / Next(handle)s, all of
+        one float type"""
+        out, dt = [], None
+        for o in operands:
+            nxt = isinstance(o, Next)
+            h = o.handle if nxt else o
+            if not isinstance(h, DataHandle):
+                raise TypeError(f"{op}: operands are DataHandles or Next(DataHandle)")
+            if h.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise ValueError(f"{op} supports float32/float64 quantities, got {h.dtype}")
+            if dt is not None and h.dtype != dt:
+                raise ValueError(f"{op}: operands mix {dt} and {h.dtype}")
+            dt = h.dtype
+            out.append((h.index, nxt))
+        return out
+
+    def _vector_boxes(self, op: str, where):
+        if isinstance(where, str):
+            if where != "all":
+                raise ValueError(f"{op}: where={where!r}")
+            return [self.local_rect(li) for li in range(self.num_local())]
+        lo, hi = where
+        return [(tuple(lo), tuple(hi)) for _ in range(self.num_local())]
+
+    def _global_sum(self, per_domain) -> float:
+        """local domains in li order, then ranks in rank order: every rank
+        computes the bitwise identical value (all ranks of a solver must
+        take the same convergence branch). World 1 does no collective."""
+        local = 0.0
+        for v in per_domain:
+            local += float(v)
+        if self.comm.world_size == 1:
+            return local
+        total = 0.0
+        for v in self.comm.allgather_object(local):
+            total += v
+        return total
+
+    def dot(self, a, b=None, where="all") -> float:
+        """GLOBAL inner product sum a(p) * b(p) (b=None: a . a) over every
+        rank's cells: `where` is "all" (each local_rect) or a global box
+        (lo, hi) applied as given on every local domain, as in
+        apply_stencil. Operands are handles (curr) or Next(handle).
+        Products and sums are in fp64 whatever the quantity type; the
+        value is deterministic and bitwise identical on every rank. Blocks
+        until the value is there (the native backend syncs the compute
+        stream of each local domain once)."""
+        (qa, na), (qb, nb) = self._vector_operands("dot", [a, a if b is None else b])
+        boxes = self._vector_boxes("dot", where)
+        return self._global_sum(self.backend.field_dot(boxes, qa, na, qb, nb))
+
+    def axpby(self, alpha: float, x, beta: float, y, out, where="all"):
+        """out = alpha * x + beta * y, element-wise in the quantity's type
+        (alpha and beta are rounded to it once). out may be the buffer of x
+        or of y. Enqueued on compute stream 0; backend.sync_compute()
+        before another stream or the exchange reads the result."""
+        (qx, nx), (qy, ny), (qo, no) = self._vector_operands("axpby", [x, y, out])
+        boxes = self._vector_boxes("axpby", where)
+        self.backend.field_axpby(boxes, float(alpha), qx, nx, float(beta), qy, ny, qo, no)
+
+    def cg_update(self, alpha: float, x, p, r) -> float:
+        """the fused conjugate-gradient update over every local_rect:
+        curr[x] += alpha * curr[p]; curr[r] -= alpha * next[p] (where
+        apply_stencil(A, p) left A p); returns the GLOBAL sum of r_new^2,
+        bitwise identical on every rank like dot()."""
+        for h in (x, p, r):
+            if not isinstance(h, DataHandle):
+                raise TypeError("cg_update: x, p and r are DataHandles")
+        (qx, _), (qp, _), (qr, _) = self._vector_operands("cg_update", [x, p, r])
+        boxes = self._vector_boxes("cg_update", "all")
+        return self._global_sum(self.backend.cg_update(boxes, float(alpha), qx, qp, qr))
 
     # ---- geometry queries ----
     def any_methods(self, m: Method) -> bool:

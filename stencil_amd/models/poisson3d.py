@@ -1,0 +1,122 @@
+"""Poisson-3D / Helmholtz-3D: solve (sigma I - laplacian) x = b with the
+conjugate-gradient solver (stencil_amd/solvers/cg.py) on the generic
+stencil operator. sigma > 0 is an implicit diffusion step or a screened
+Poisson problem; sigma = 0 is the Poisson problem proper, which needs a
+boundary that pins the constant (FIXED(0) or ANTIMIRROR on some axis).
+
+Four quantities x, b, r, p; only p (every iteration) and x (for a nonzero
+initial guess) are ever exchanged, each in an exchange group of its own.
+The radius is the operator's, so the exchange moves faces only.
+"""
+from __future__ import annotations
+
+from typing import List, Optional
+
+import numpy as np
+
+from ..boundary import FACES, Boundary, parse_face
+from ..core import DistributedDomain
+from ..parallel.placement import PlacementStrategy
+from ..solvers.cg import CGResult, ConjugateGradient
+from ..stencil import Stencil
+
+
+class Poisson3D:
+    def __init__(
+        self,
+        size,
+        order: int = 2,
+        dtype=np.float32,
+        sigma: float = 0.0,
+        spacing=(1.0, 1.0, 1.0),
+        backend: str = "native",
+        gpus: Optional[List[int]] = None,
+        boundary=None,
+        placement: PlacementStrategy = PlacementStrategy.NodeAware,
+        device: str = "cpu",
+    ):
+        """A = sigma I - laplacian(order, spacing); sigma >= 0.
+
+        boundary: {face: kind | (kind, value)} as in Diffusion3D, applied
+        to all four quantities; None = fully periodic. The kinds the
+        solver accepts are PERIODIC, FIXED(0), MIRROR and ANTIMIRROR; fold
+        inhomogeneous Dirichlet data into the right-hand side. Raises
+        ValueError when the problem is singular: sigma == 0 with every axis
+        periodic or MIRROR (the constant is then in A's null space)."""
+        sigma = float(sigma)
+        if not sigma >= 0.0:
+            raise ValueError(f"Poisson3D: sigma must be >= 0, got {sigma}")
+        self.sigma = sigma
+        self.stencil = -Stencil.laplacian(order, spacing)
+        if sigma != 0.0:
+            self.stencil = self.stencil + sigma * Stencil.identity()
+        kinds = {}
+        if boundary:
+            for face, spec in boundary.items():
+                kind = spec[0] if isinstance(spec, (tuple, list)) else spec
+                for f in parse_face(face):
+                    kinds[FACES[f]] = Boundary(kind)
+        if sigma == 0.0 and all(
+            kinds.get(f, Boundary.PERIODIC) in (Boundary.PERIODIC, Boundary.MIRROR)
+            for f in FACES
+        ):
+            raise ValueError(
+                "Poisson3D: sigma == 0 with every axis periodic or MIRROR is singular "
+                "(constants are in the null space); use sigma > 0 or a FIXED(0)/ANTIMIRROR face"
+            )
+        self.dd = DistributedDomain(*size, backend=backend, device=device)
+        self.dd.set_radius(self.stencil.radius())
+        self.dd.set_placement(placement)
+        if gpus is not None:
+            self.dd.set_gpus(gpus)
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"Poisson3D supports float32/float64, got {dt}")
+        self.x = self.dd.add_data(dt, "x")
+        self.b = self.dd.add_data(dt, "b")
+        self.r = self.dd.add_data(dt, "r")
+        self.p = self.dd.add_data(dt, "p")
+        # quantities in no group are never exchanged: b and r need no halos
+        self.dd.set_exchange_groups([[self.p.index], [self.x.index]])
+        if boundary:
+            for face, spec in boundary.items():
+                kind, value = spec if isinstance(spec, (tuple, list)) else (spec, 0)
+                self.dd.set_boundary(face, kind, value)
+        self.cg: Optional[ConjugateGradient] = None
+
+    def realize(self):
+        self.dd.realize()
+        self.cg = ConjugateGradient(self.dd, self.stencil, self.x, self.b, self.r, self.p,
+                                    group_p=0, group_x=1)
+
+    def _scatter(self, handle, g):
+        g = np.asarray(g)
+        want = (self.dd.size[2], self.dd.size[1], self.dd.size[0])
+        if g.shape != want:
+            raise ValueError(f"Poisson3D: want a (z, y, x) array of shape {want}, got {g.shape}")
+        for li in range(self.dd.num_local()):
+            lo, hi = self.dd.local_rect(li)
+            block = np.ascontiguousarray(g[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]])
+            self.dd.write_global(li, lo, block.astype(handle.dtype), handle)
+
+    def set_rhs(self, global_array):
+        """b = the (z, y, x) global array; each rank writes its own cells"""
+        self._scatter(self.b, global_array)
+
+    def set_guess(self, global_array):
+        """x = the global array, for solve(x0_zero=False)"""
+        self._scatter(self.x, global_array)
+
+    def solve(self, tol: float = 1e-6, max_iter: int = 1000, x0_zero: bool = True,
+              overlap: bool = True) -> CGResult:
+        if self.cg is None:
+            self.realize()
+        return self.cg.solve(tol=tol, max_iter=max_iter, x0_zero=x0_zero, overlap=overlap)
+
+    def solution(self) -> np.ndarray:
+        """x as a (z, y, x) global array; cells of other ranks' domains are 0"""
+        out = np.zeros((self.dd.size[2], self.dd.size[1], self.dd.size[0]), dtype=self.x.dtype)
+        for li in range(self.dd.num_local()):
+            lo, hi = self.dd.local_rect(li)
+            out[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]] = self.dd.read_global(li, lo, hi, self.x)
+        return out

@@ -698,6 +698,48 @@ class NativeBackend:
             self._stencil_taps[id(stencil)] = taps
         _C.stencil_apply(self.engine, li, src_qi, dst_qi, _rect3(lo, hi), taps[1], ty, stream_id)
 
+    # ---- vector operations (csrc/src/vector_ops.hip) ----
+    # `boxes` holds one global box (lo, hi) per local domain; an operand is
+    # (quantity index, next_buf). The reductions return one fp64 sum per
+    # local domain: every domain's kernel is launched before the first
+    # wait, so a reduction costs one host sync per domain.
+    def field_dot(self, boxes, a: int, a_next: bool, b: int, b_next: bool,
+                  stream_id: int = 0) -> List[float]:
+        """per local domain: sum of a * b over its box, products and sums
+        in fp64, deterministic. ValueError (nothing launched) on an unknown
+        quantity, a non-float32/float64 or mixed element size, or a box
+        outside the allocation."""
+        n = 0
+        try:
+            for li, (lo, hi) in enumerate(boxes):
+                _C.field_dot_begin(self.engine, li, a, a_next, b, b_next, _rect3(lo, hi),
+                                   stream_id)
+                n += 1
+        finally:
+            out = [_C.reduction_end(self.engine, li) for li in range(n)]
+        return out
+
+    def field_axpby(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
+                    y_next: bool, out: int, out_next: bool, stream_id: int = 0):
+        """out = alpha * x + beta * y over each local domain's box, in the
+        quantity's type; out may alias x or y. Enqueued, not awaited."""
+        for li, (lo, hi) in enumerate(boxes):
+            _C.field_axpby(self.engine, li, alpha, x, x_next, beta, y, y_next, out, out_next,
+                           _rect3(lo, hi), stream_id)
+
+    def cg_update(self, boxes, alpha: float, x: int, p: int, r: int,
+                  stream_id: int = 0) -> List[float]:
+        """fused CG update per local domain: curr[x] += alpha * curr[p];
+        curr[r] -= alpha * next[p]; returns each domain's sum of r_new^2"""
+        n = 0
+        try:
+            for li, (lo, hi) in enumerate(boxes):
+                _C.cg_update_begin(self.engine, li, alpha, x, p, r, _rect3(lo, hi), stream_id)
+                n += 1
+        finally:
+            out = [_C.reduction_end(self.engine, li) for li in range(n)]
+        return out
+
     def jacobi_graph_create(self, li: int, qi: int, region_lo: Vec, region_hi: Vec,
                             c_lo: Vec, c_hi: Vec) -> int:
         """whole-step replay graph (single-process single-domain path);

@@ -10,18 +10,29 @@ stream of the given ExchangeEngine; regions are global-coordinate Rect3s.
   (csrc/src/stencil_op.hip; StencilTaps / StencilType are its arguments)
 - fill_f32 / init_harmonic_f64: field initialization (csrc/src/init.hip)
 - field_stats: min/max/RMS reduction (csrc/src/reductions.hip)
+- field_dot / field_axpby / cg_update: deterministic inner product,
+  out = alpha x + beta y and the fused conjugate-gradient update on pitched
+  quantities (csrc/src/vector_ops.hip); field_dot_begin / cg_update_begin
+  + reduction_end split a reduction so that several local domains launch
+  before any of them waits
 """
 from .._C import (  # noqa: F401
     FieldStats,
     MhdCoeffs,
     StencilTaps,
     StencilType,
+    cg_update,
+    cg_update_begin,
+    field_axpby,
+    field_dot,
+    field_dot_begin,
     field_stats,
     fill_f32,
     init_harmonic_f64,
     jacobi_step,
     mhd_div_pass,
     mhd_substep,
+    reduction_end,
     stencil_apply,
 )
 
@@ -30,11 +41,17 @@ __all__ = [
     "MhdCoeffs",
     "StencilTaps",
     "StencilType",
+    "cg_update",
+    "cg_update_begin",
+    "field_axpby",
+    "field_dot",
+    "field_dot_begin",
     "field_stats",
     "fill_f32",
     "init_harmonic_f64",
     "jacobi_step",
     "mhd_div_pass",
     "mhd_substep",
+    "reduction_end",
     "stencil_apply",
 ]

@@ -1,0 +1,194 @@
+"""Conjugate gradients for A x = b with A a symmetric positive definite
+stencil operator.
+
+The operator is a `Stencil` applied by `DistributedDomain.apply_stencil`;
+the halo exchange and the boundary fill of the quantity `p` supply the
+neighbour values, so the domain's boundary kinds ARE the discrete boundary
+conditions of A. The solver never calls `dd.swap()`: `A p` lives in the
+next buffer of `p`, where apply_stencil leaves it, so four quantities
+(x, b, r, p) are all the storage there is.
+
+    r = b            (x0_zero)   or   exchange(group_x); next[x] = A x; r = b - next[x]
+    p = r; rr = dot(r, r); bb = dot(b, b)
+    repeat:  interior(A, p) || exchange(group_p); exterior; sync    -> next[p] = A p
+             alpha = rr / dot(p, Next(p))
+             rr_new = cg_update(alpha, x, p, r)
+             stop if rr_new <= tol^2 * bb
+             p = r + (rr_new / rr) * p ;  rr = rr_new
+
+Boundary conditions. CG needs A symmetric, and linear and homogeneous in
+the field: PERIODIC, FIXED(0), MIRROR and ANTIMIRROR qualify (for star
+stencils: `u . A v == v . A u` was checked to rounding for the Laplacians
+of order 2, 4 and 8 under each of them; for stencils with edge or corner
+taps under non-periodic boundaries symmetry is not vouched for). OPEN,
+CLAMP and FIXED(c != 0) are refused. Inhomogeneous Dirichlet data is the
+caller's job: fold it into b (b -= A applied to the field that holds the
+boundary values in its halo and 0 inside).
+
+Every scalar the iteration branches on comes from `dd.dot` /
+`dd.cg_update`, which return the bitwise identical value on every rank, so
+all ranks stop in the same iteration for the same reason.
+"""
+from __future__ import annotations
+
+import math
+import time
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import numpy as np
+
+from ..boundary import Boundary
+from ..core import DataHandle, DistributedDomain, Next
+from ..stencil import Stencil
+
+
+@dataclass
+class CGResult:
+    converged: bool
+    iterations: int
+    # relative recursive residual norm sqrt(r.r / b.b) after each iteration;
+    # entry 0 is the initial one (1.0 when x0 = 0)
+    residuals: List[float] = field(default_factory=list)
+    reason: str = ""  # "converged" | "max_iter" | "breakdown" | "zero_rhs"
+
+
+_FACES = ("x-", "x+", "y-", "y+", "z-", "z+")
+
+
+class ConjugateGradient:
+    def __init__(self, dd: DistributedDomain, operator: Stencil, x: DataHandle, b: DataHandle,
+                 r: DataHandle, p: DataHandle, group_p: int = 0,
+                 group_x: Optional[int] = None):
+        """dd is realized and holds x, b, r and p, four distinct quantities
+        of one float type. group_p is the exchange group that moves p's
+        halos (every iteration); group_x the one that moves x's (needed for
+        solve(x0_zero=False) only). Raises ValueError for a non-symmetric
+        stencil, a domain radius that does not cover it, mixed dtypes and a
+        boundary kind on p or x other than PERIODIC, FIXED(0), MIRROR or
+        ANTIMIRROR."""
+        if not dd._realized:
+            raise ValueError("ConjugateGradient: construct after dd.realize()")
+        hs = (x, b, r, p)
+        if len({h.index for h in hs}) != 4:
+            raise ValueError("ConjugateGradient: x, b, r and p must be four distinct quantities")
+        dt = x.dtype
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"ConjugateGradient supports float32/float64 quantities, got {dt}")
+        if any(h.dtype != dt for h in hs):
+            raise ValueError(
+                "ConjugateGradient: x, b, r and p must share one dtype, got "
+                + ", ".join(str(h.dtype) for h in hs)
+            )
+        if not operator.is_symmetric():
+            raise ValueError("ConjugateGradient: the stencil is not symmetric (w(o) != w(-o))")
+        need = operator.radius()
+        for dz in (-1, 0, 1):
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    if (dx, dy, dz) != (0, 0, 0) and dd.radius.dir(dx, dy, dz) < need.dir(dx, dy, dz):
+                        raise ValueError(
+                            f"ConjugateGradient: the domain's radius {dd.radius.dir(dx, dy, dz)} in "
+                            f"direction {(dx, dy, dz)} does not cover the stencil's "
+                            f"{need.dir(dx, dy, dz)}"
+                        )
+        groups = dd.exchange_groups or [list(range(len(dd._data)))]
+        if not (0 <= group_p < len(groups) and p.index in groups[group_p]):
+            raise ValueError(f"ConjugateGradient: p is not in exchange group {group_p}")
+        if group_x is not None and not (0 <= group_x < len(groups) and x.index in groups[group_x]):
+            raise ValueError(f"ConjugateGradient: x is not in exchange group {group_x}")
+        spec = dd.boundary
+        if spec is not None:
+            for h in (p, x):
+                for a in range(3):
+                    if spec.periodic[a]:
+                        continue
+                    for s in (0, 1):
+                        k = spec.kind(h.index, a, s)
+                        ok = k in (Boundary.MIRROR, Boundary.ANTIMIRROR) or (
+                            k == Boundary.FIXED and float(spec.value(h.index, a, s)) == 0.0
+                        )
+                        if not ok:
+                            raise ValueError(
+                                f"ConjugateGradient: boundary {k.name} on face {_FACES[2 * a + s]} "
+                                f"of quantity {h.name or h.index}: the operator must be symmetric, "
+                                "linear and homogeneous (PERIODIC, FIXED(0), MIRROR or ANTIMIRROR); "
+                                "fold inhomogeneous boundary data into b"
+                            )
+        self.dd, self.A = dd, operator
+        self.x, self.b, self.r, self.p = x, b, r, p
+        self.group_p, self.group_x = group_p, group_x
+        # host wall time per phase of the last solve (each phase ends in a
+        # host sync): operator = apply + exchange, dot = p . A p,
+        # update = cg_update + the p update
+        self.phase_times = {"operator": 0.0, "dot": 0.0, "update": 0.0}
+
+    def _apply(self, h: DataHandle, group: int, overlap: bool):
+        """next[h] = A curr[h] on every local domain, halos refreshed"""
+        dd = self.dd
+        if overlap:
+            dd.apply_stencil(self.A, h, where="interior")
+            dd.exchange(group)
+            dd.apply_stencil(self.A, h, where="exterior")
+        else:
+            dd.exchange(group)
+            dd.apply_stencil(self.A, h, where="all")
+        dd.backend.sync_compute()
+
+    def solve(self, tol: float = 1e-6, max_iter: int = 1000, x0_zero: bool = True,
+              overlap: bool = True) -> CGResult:
+        """iterate until ||r|| <= tol * ||b|| (recursive residual) or
+        max_iter. x0_zero=True starts from x = 0 (x's content is
+        overwritten); False starts from curr[x] and needs group_x.
+        b = 0 gives x = 0 in 0 iterations. A non-positive or non-finite
+        p . A p ends the solve with converged=False, reason="breakdown"."""
+        dd, x, b, r, p = self.dd, self.x, self.b, self.r, self.p
+        self.phase_times = {k: 0.0 for k in self.phase_times}
+        if not x0_zero and self.group_x is None:
+            raise ValueError("solve(x0_zero=False) needs group_x, the exchange group of x")
+        bb = dd.dot(b)
+        if not math.isfinite(bb):
+            return CGResult(False, 0, [float("nan")], "breakdown")
+        if bb == 0.0:
+            dd.axpby(0.0, b, 0.0, b, out=x)  # b is all zeros: so is x
+            dd.backend.sync_compute()
+            return CGResult(True, 0, [0.0], "zero_rhs")
+        if x0_zero:
+            dd.axpby(0.0, b, 0.0, b, out=x)
+            dd.axpby(1.0, b, 0.0, b, out=r)
+        else:
+            self._apply(x, self.group_x, overlap)
+            dd.axpby(1.0, b, -1.0, Next(x), out=r)
+        dd.axpby(1.0, r, 0.0, r, out=p)
+        rr = dd.dot(r)
+        dd.backend.sync_compute()  # the exchange reads p on other streams
+        residuals = [math.sqrt(rr / bb)] if math.isfinite(rr) else [float("nan")]
+        if not math.isfinite(rr):
+            return CGResult(False, 0, residuals, "breakdown")
+        limit = tol * tol * bb
+        if rr <= limit:
+            return CGResult(True, 0, residuals, "converged")
+        for it in range(1, max_iter + 1):
+            t0 = time.perf_counter()
+            self._apply(p, self.group_p, overlap)
+            t1 = time.perf_counter()
+            pap = dd.dot(p, Next(p))
+            t2 = time.perf_counter()
+            self.phase_times["operator"] += t1 - t0
+            self.phase_times["dot"] += t2 - t1
+            if not (math.isfinite(pap) and pap > 0.0):
+                return CGResult(False, it - 1, residuals, "breakdown")
+            alpha = rr / pap
+            rr_new = dd.cg_update(alpha, x, p, r)
+            if not math.isfinite(rr_new):
+                self.phase_times["update"] += time.perf_counter() - t2
+                return CGResult(False, it, residuals + [float("nan")], "breakdown")
+            residuals.append(math.sqrt(rr_new / bb))
+            if rr_new <= limit:
+                self.phase_times["update"] += time.perf_counter() - t2
+                return CGResult(True, it, residuals, "converged")
+            dd.axpby(1.0, r, rr_new / rr, p, out=p)
+            dd.backend.sync_compute()  # before the next exchange reads p
+            rr = rr_new
+            self.phase_times["update"] += time.perf_counter() - t2
+        return CGResult(False, max_iter, residuals, "max_iter")

@@ -182,6 +182,13 @@ class Stencil:
         """every tap has at most one nonzero component"""
         return all(sum(c != 0 for c in o) <= 1 for o in self._taps)
 
+    def is_symmetric(self) -> bool:
+        """w(o) == w(-o) for every tap: on a periodic grid the operator is
+        then a symmetric matrix (what conjugate gradients needs)"""
+        return all(
+            self._taps.get((-o[0], -o[1], -o[2])) == w for o, w in self._taps.items()
+        )
+
     def radius(self) -> "_C.Radius":
         """minimal Radius that makes every read legal. Face radii are the
         extreme offsets per side; an edge/corner direction e is nonzero iff

@@ -343,5 +343,64 @@ class TorchBackend:
             acc += torch.tensor(w, dtype=tdt, device=src.device) * src[dom._sl(p, ext)]
         dom.next[dst_qi][dom._sl(pos, ext)] = acc
 
+    # ---- vector operations: slicing references of csrc/src/vector_ops.hip ----
+    def _vector_views(self, op, li, lo, hi, operands):
+        """validated tensor views of the operands over the global box
+        [lo, hi) of local domain li (None for an empty box); the native
+        ops' checks, as ValueErrors"""
+        dom = self.domains[li]
+        es = None
+        for qi, _nxt in operands:
+            if not 0 <= qi < len(dom.elem_sizes):
+                raise ValueError(f"{op}: no such quantity")
+            if dom.elem_sizes[qi] not in (4, 8):
+                raise ValueError(
+                    f"{op}: float32/float64 quantities only (element size {dom.elem_sizes[qi]})"
+                )
+            if es is not None and dom.elem_sizes[qi] != es:
+                raise ValueError(f"{op}: operands differ in element size")
+            es = dom.elem_sizes[qi]
+        ext = tuple(hi[i] - lo[i] for i in range(3))
+        if min(ext) <= 0:
+            return None
+        flo, raw = dom.full_lo(), dom.raw_size()
+        pos = tuple(lo[i] - flo[i] for i in range(3))
+        if any(pos[i] < 0 or pos[i] + ext[i] > raw[i] for i in range(3)):
+            raise ValueError(f"{op}: region {lo}..{hi} is outside the allocation")
+        return [dom.region(qi, pos, ext, nxt) for qi, nxt in operands]
+
+    def field_dot(self, boxes, a, a_next, b, b_next, stream_id=0):
+        """per local domain: sum of a * b over its box, products and sums in fp64"""
+        out = []
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_dot", li, lo, hi, [(a, a_next), (b, b_next)])
+            out.append(0.0 if v is None else float((v[0].double() * v[1].double()).sum()))
+        return out
+
+    def field_axpby(self, boxes, alpha, x, x_next, beta, y, y_next, out, out_next, stream_id=0):
+        """out = alpha * x + beta * y in the quantity's type, alpha and beta
+        rounded to it once; two products and one sum, no FMA"""
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_axpby", li, lo, hi,
+                                   [(x, x_next), (y, y_next), (out, out_next)])
+            if v is None:
+                continue
+            tx, ty, tout = v
+            al = torch.tensor(alpha, dtype=tx.dtype, device=tx.device)
+            be = torch.tensor(beta, dtype=tx.dtype, device=tx.device)
+            tout.copy_(al * tx + be * ty)
+
+    def cg_update(self, boxes, alpha, x, p, r, stream_id=0):
+        """the unfused composition: x = 1 x + alpha p; r = 1 r + (-alpha) A p
+        (A p in next[p]); returns each domain's dot(r, r)"""
+        if x == p or x == r or p == r:
+            raise ValueError("cg_update: x, p and r must be distinct quantities")
+        for li, (lo, hi) in enumerate(boxes):  # validate every operand before any write
+            self._vector_views("cg_update", li, lo, hi,
+                               [(x, False), (p, False), (p, True), (r, False)])
+        self.field_axpby(boxes, 1.0, x, False, alpha, p, False, x, False)
+        self.field_axpby(boxes, 1.0, r, False, -alpha, p, True, r, False)
+        return self.field_dot(boxes, r, False, r, False)
+
     def sync_compute(self):
         pass
