@@ -16,10 +16,18 @@ namespace stencil_amd {
 // LATER kernel on the SAME stream rewrites) is discard-safe and the
 // domain has radius >= 1 -- the caller asserts this (the overlap
 // interior and full-rect launches qualify).
+// A row is only ever extended into cells of its own row (x halo, local
+// rect) or pitch-slack bytes; where that room is missing the launch is not
+// extended. Throws std::invalid_argument, and launches nothing, for an
+// unknown domain or quantity, a non-fp32 quantity, an extendVec outside
+// 0..2 and a region whose 1-cell apron leaves full_region() (the graph
+// creators below check the same).
 void jacobi_step(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
                  const Rect3 &computeRegion, int streamId = 0, int extendVec = 0);
 
-// fill an fp32 region with `value` (curr or next buffer)
+// fill an fp32 region with `value` (curr or next buffer); throws
+// std::invalid_argument, launching nothing, unless region is inside
+// full_region()
 void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, float value,
               bool nextBuf);
 

@@ -307,10 +307,32 @@ PYBIND11_MODULE(_C, m) {
             hipMemcpy((void *)e.buffer_ptr(buf), s.data(), s.size(), hipMemcpyHostToDevice));
       });
 
-  m.def("jacobi_step", &jacobi_step, py::arg("eng"), py::arg("dom"), py::arg("qi"),
-        py::arg("region"), py::arg("compute_region"), py::arg("stream_id") = 0,
-        py::arg("extend_vec") = 0);
-  m.def("fill_f32", &fill_f32);
+  // invalid arguments (std::invalid_argument) surface as ValueErrors
+  auto value_errors = [](auto &&call) {
+    try {
+      return call();
+    } catch (const std::invalid_argument &e) {
+      throw py::value_error(e.what());
+    }
+  };
+  m.def(
+      "jacobi_step",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                     const Rect3 &computeRegion, int streamId, int extendVec) {
+        value_errors([&] {
+          jacobi_step(eng, dom, qi, region, computeRegion, streamId, extendVec);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("region"),
+      py::arg("compute_region"), py::arg("stream_id") = 0, py::arg("extend_vec") = 0);
+  m.def("fill_f32", [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                                   float value, bool nextBuf) {
+    value_errors([&] {
+      fill_f32(eng, dom, qi, region, value, nextBuf);
+      return 0;
+    });
+  });
 
   // generic weighted stencil (csrc/src/stencil_op.hip)
   py::class_<StencilTaps>(m, "StencilTaps")
@@ -334,13 +356,6 @@ PYBIND11_MODULE(_C, m) {
       py::arg("taps"), py::arg("type"), py::arg("stream_id") = 0);
 
   // vector operations (csrc/src/vector_ops.hip); invalid arguments are ValueErrors
-  auto value_errors = [](auto &&call) {
-    try {
-      return call();
-    } catch (const std::invalid_argument &e) {
-      throw py::value_error(e.what());
-    }
-  };
   m.def(
       "field_dot",
       [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
@@ -400,14 +415,30 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("eng"), py::arg("dom"));
 
-  m.def("jacobi_graph_create", &jacobi_graph_create, py::arg("eng"), py::arg("dom"),
-        py::arg("qi"), py::arg("region"), py::arg("compute_region"));
+  m.def(
+      "jacobi_graph_create",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                     const Rect3 &computeRegion) {
+        return value_errors(
+            [&] { return jacobi_graph_create(eng, dom, qi, region, computeRegion); });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("region"),
+      py::arg("compute_region"));
   m.def("jacobi_graph_launch", &jacobi_graph_launch, py::arg("handle"), py::arg("n_steps") = 1);
   m.def("jacobi_graph_sync", &jacobi_graph_sync);
   m.def("jacobi_graph_is_wrap", &jacobi_graph_is_wrap);
-  m.def("jacobi_mr_graph_create", &jacobi_mr_graph_create, py::arg("eng"), py::arg("dom"),
-        py::arg("qi"), py::arg("interior"), py::arg("compute_region"), py::arg("exteriors"),
-        py::arg("extend_vec") = 2);
+  m.def(
+      "jacobi_mr_graph_create",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
+                     const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
+                     int extendVec) {
+        return value_errors([&] {
+          return jacobi_mr_graph_create(eng, dom, qi, interior, computeRegion, exteriors,
+                                        extendVec);
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("interior"),
+      py::arg("compute_region"), py::arg("exteriors"), py::arg("extend_vec") = 2);
   m.def("jacobi_mr_graph_stream", &jacobi_mr_graph_stream);
   m.def("jacobi_mr_graph_pre", &jacobi_mr_graph_pre);
   m.def("jacobi_mr_graph_post", &jacobi_mr_graph_post);

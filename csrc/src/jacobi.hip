@@ -32,6 +32,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <memory>
+#include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -158,9 +160,11 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4(JacobiParams p) {
   };
 
   const int64_t a0 = p.loX - p.allocX;
-  // vecAll: host pre-adjusted loX/extX (16B-aligned start, extX%4==0,
-  // writes beyond the true region land only in halo/row-slack bytes that
-  // the next exchange refreshes before any read) -- no scalar lanes.
+  // vecAll: host pre-adjusted loX/extX (16B-aligned start, extX%4==0;
+  // the launcher's row_extension guarantees that writes beyond the true
+  // region land only in same-row halo / local-rect cells, which the next
+  // exchange or a later kernel rewrites before any read, or in pitch-slack
+  // bytes where the row has them) -- no scalar lanes.
   // Otherwise head = elements until the next 16 B-aligned ADDRESS (the
   // allocation pad shifts the base, so index-aligned units would issue
   // misaligned dwordx4 -- measured ~10% on gfx950); must match the
@@ -237,8 +241,10 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4(JacobiParams p) {
 // the row's last true cell, the last lane loads `right` from its first, and
 // a per-lane select feeds that scalar to the one component whose in-vector
 // neighbour is an overshoot cell. Overshoot components still compute and
-// store garbage into halo / pitch-slack bytes, which nothing on this path
-// reads.
+// store garbage. The launcher only extends a row when every overshoot cell
+// is an x-halo cell or a pitch-slack byte of that row (row_extension), which
+// nothing on this path reads; a row without that room never gets here
+// (jacobi_wrap_eligible answers false).
 // gfx950 resource usage (-Rpass-analysis=kernel-resource-usage), the same
 // for ZC = 16 and 32:
 //   WRAP=false: 58 VGPRs, 54 SGPRs, 0 scratch, 8 waves/SIMD, 12288 B LDS
@@ -457,6 +463,75 @@ bool jac_use_lds() {
   return useLds != 0;
 }
 
+bool rect_inside(const Rect3 &r, const Rect3 &full) {
+  return r.lo.x >= full.lo.x && r.lo.y >= full.lo.y && r.lo.z >= full.lo.z &&
+         r.hi.x <= full.hi.x && r.hi.y <= full.hi.y && r.hi.z <= full.hi.z;
+}
+
+// Argument check of every jacobi entry point, before anything is launched
+// or captured: the kernels read a 1-cell apron around `region`, and all of
+// it has to lie inside the allocation. An empty region is a no-op and valid.
+LocalDomain &checked_jacobi_domain(ExchangeEngine &eng, int dom, int64_t qi, const char *name) {
+  if (dom < 0 || dom >= eng.num_domains())
+    throw std::invalid_argument(std::string(name) + ": no such domain " + std::to_string(dom));
+  LocalDomain &d = eng.domain(dom);
+  if (qi < 0 || qi >= d.num_data())
+    throw std::invalid_argument(std::string(name) + ": no such quantity");
+  if (d.elem_size(qi) != 4)
+    throw std::invalid_argument(std::string(name) + ": quantity must be fp32");
+  return d;
+}
+
+void check_jacobi_region(const LocalDomain &d, const Rect3 &region, const char *name) {
+  const Vec3 ext = region.extent();
+  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return;
+  if (ext.x > 0x7fffffff || ext.y > 0x7fffffff || ext.z > 0x7fffffff)
+    throw std::invalid_argument(std::string(name) + ": region extent exceeds 2^31 - 1");
+  const Rect3 full = d.full_region();
+  const Rect3 apron(region.lo - Vec3(1, 1, 1), region.hi + Vec3(1, 1, 1));
+  if (!rect_inside(apron, full))
+    throw std::invalid_argument(std::string(name) + ": region " + region.str() +
+                                " plus its 1-cell apron leaves the allocation " + full.str());
+}
+
+// Row extension of a pure-vector (vecAll) launch: the x range of `region`
+// grown left by `under` cells to the previous 16 B-aligned ADDRESS and right
+// by `over` cells to a multiple of 4, which removes the scalar head/tail
+// lanes (the probe measured them at ~10% of the kernel). Returns false when
+// the launch must stay as it is.
+//   mode 1 (free): the extended cells are written with discardable values,
+//     so each must be an x-halo cell or a local-rect cell of the SAME row,
+//     or a pitch-slack byte. Rows are `pitch` apart and hold raw_size().x
+//     cells: the extended range has to stay within [-slack, raw.x + slack)
+//     of its own row, slack = pitch / 4 - raw.x. A row without slack
+//     ((X + 2r) % 64 == 0) that would be overrun is NOT extended: the
+//     overshoot would land in cells of the neighbouring rows, which other
+//     lanes of the same launch (or nobody) own.
+//   mode 2 (strict): no cell outside the region may be written; only a
+//     region that is aligned already qualifies.
+// Alignment is the same for both buffer parities (same pad, 256 B-aligned
+// allocations), so the answer holds for every launch of the region.
+bool row_extension(const LocalDomain &d, int64_t qi, const Rect3 &region, int mode,
+                   int64_t &under, int64_t &over) {
+  under = over = 0;
+  const int64_t extX = region.extent().x;
+  if (!mode || extX < 8) return false;
+  const int64_t a0 = region.lo.x - d.full_region().lo.x;
+  const uintptr_t addr0 = (uintptr_t)d.curr(qi).ptr + (uintptr_t)(a0 * 4);
+  const int64_t u = (int64_t)((addr0 & 15) >> 2);
+  const int64_t o = (4 - ((extX + u) & 3)) & 3;
+  if (mode == 2) {
+    if (u != 0 || o != 0) return false;
+  } else {
+    const int64_t rowCells = d.raw_size().x;
+    const int64_t slack = d.curr(qi).pitch / 4 - rowCells;
+    if (a0 - u < -slack || a0 + extX + o > rowCells + slack) return false;
+  }
+  under = u;
+  over = o;
+  return true;
+}
+
 // shared launch logic: builds params from the domain's CURRENT buffer
 // parity and enqueues the right kernel variant onto `stream`. Also used
 // by the whole-step hipGraph capture (pointers get baked per parity).
@@ -474,9 +549,8 @@ bool jac_use_lds() {
 void launch_jacobi_on(LocalDomain &d, int64_t qi, const Rect3 &region,
                       const Rect3 &computeRegion, hipStream_t stream, int fullRectVec = 0,
                       bool wrap = false) {
-  if (d.elem_size(qi) != 4) throw std::runtime_error("jacobi_step: quantity must be fp32");
   Vec3 ext = region.extent();
-  if (ext.flatten() <= 0) return;
+  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return;
   JacobiParams p{};
   p.src = d.curr(qi).ptr;
   p.dst = d.next(qi).ptr;
@@ -498,26 +572,18 @@ void launch_jacobi_on(LocalDomain &d, int64_t qi, const Rect3 &region,
   p.cHiX = computeRegion.hi.x;
   p.cHiY = computeRegion.hi.y;
   p.cHiZ = computeRegion.hi.z;
-  // fullRectVec: the region is the whole interior rect (radius >= 1 on
-  // both x sides). Extend it left to the previous 16 B-aligned ADDRESS
-  // and right to a multiple of 4, eliminating the scalar head/tail lanes
-  // (the probe measured them at ~10% of the kernel). The extended cells
-  // are x-halo cells or pitch-slack bytes of the adjacent row: every one
-  // is rewritten by the next exchange (or is padding) before any read,
-  // and never a translate SOURCE (sources are interior cells).
-  if (fullRectVec && ext.x >= 8) {
-    const int64_t a0 = region.lo.x - full.lo.x;
-    const uintptr_t addr0 = (uintptr_t)p.src + a0 * 4;
-    const int64_t under = (int64_t)((addr0 & 15) >> 2);
-    int64_t e2 = ext.x + under;
-    const int64_t over = (4 - (e2 & 3)) & 3;
-    e2 += over;
-    if (fullRectVec != 2 || (under == 0 && over == 0)) {
-      p.loX = region.lo.x - under;
-      p.extX = (int32_t)e2;
-      p.vecAll = 1;
-      ext.x = e2;
-    }
+  // fullRectVec: pure-vector launch over the row-extended region where
+  // row_extension allows it. The extended cells are x-halo cells, cells of
+  // the local rect in the same row (a later same-stream kernel rewrites
+  // them) or pitch-slack bytes: every one is rewritten by the next exchange
+  // (or is padding) before any read, and never a translate SOURCE (sources
+  // are interior cells).
+  int64_t under, over;
+  if (row_extension(d, qi, region, fullRectVec, under, over)) {
+    p.loX = region.lo.x - under;
+    p.extX = (int32_t)(ext.x + under + over);
+    p.vecAll = 1;
+    ext.x = p.extX;
   }
   const bool useLds = jac_use_lds();
   if (wrap && !(p.vecAll && useLds))
@@ -581,7 +647,10 @@ void launch_jacobi_on(LocalDomain &d, int64_t qi, const Rect3 &region,
 
 void jacobi_step(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
                  const Rect3 &computeRegion, int streamId, int extendVec) {
-  LocalDomain &d = eng.domain(dom);
+  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "jacobi_step");
+  check_jacobi_region(d, region, "jacobi_step");
+  if (extendVec < 0 || extendVec > 2)
+    throw std::invalid_argument("jacobi_step: extend_vec must be 0, 1 or 2");
   STENCIL_HIP(hipSetDevice(d.gpu()));
   launch_jacobi_on(d, qi, region, computeRegion, eng.compute_stream(dom, streamId),
                    extendVec);
@@ -618,7 +687,10 @@ bool jacobi_wrap_eligible(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 
   const LocalDomain &d = eng.domain(dom);
   if (d.elem_size(qi) != 4) return false;
   if (!(region == d.compute_region()) || !(region == computeRegion)) return false;
-  return region.extent().x >= 8 && jac_use_lds();
+  // the wrap kernel is a vecAll launch: rows that cannot be extended
+  // (row_extension) fall back to the translate graph
+  int64_t under, over;
+  return jac_use_lds() && row_extension(d, qi, region, /*mode=*/1, under, over);
 }
 
 } // namespace
@@ -640,7 +712,8 @@ int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect
   // table swap leaves the graph too (jacobi_graph_launch hoists it).
   // Halos are STALE after steps taken on this path until the next
   // exchange(); interior cells are exact.
-  LocalDomain &d = eng.domain(dom);
+  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "jacobi_graph_create");
+  check_jacobi_region(d, region, "jacobi_graph_create");
   STENCIL_HIP(hipSetDevice(d.gpu()));
   auto sg = std::make_unique<StepGraph>();
   sg->eng = &eng;
@@ -722,7 +795,11 @@ std::vector<std::unique_ptr<MrStepGraph>> g_mrGraphs;
 int64_t jacobi_mr_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
                                const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
                                int extendVec) {
-  LocalDomain &d = eng.domain(dom);
+  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "jacobi_mr_graph_create");
+  check_jacobi_region(d, interior, "jacobi_mr_graph_create");
+  for (const Rect3 &box : exteriors) check_jacobi_region(d, box, "jacobi_mr_graph_create");
+  if (extendVec < 0 || extendVec > 2)
+    throw std::invalid_argument("jacobi_mr_graph_create: extend_vec must be 0, 1 or 2");
   STENCIL_HIP(hipSetDevice(d.gpu()));
   auto sg = std::make_unique<MrStepGraph>();
   sg->eng = &eng;
@@ -777,11 +854,15 @@ void jacobi_mr_graph_sync(int64_t handle) {
 
 void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, float value,
               bool nextBuf) {
-  LocalDomain &d = eng.domain(dom);
-  if (d.elem_size(qi) != 4) throw std::runtime_error("fill_f32: quantity must be fp32");
+  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "fill_f32");
   const Vec3 ext = region.extent();
-  if (ext.flatten() <= 0) return;
+  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return;
+  if (ext.x > 0x7fffffff || ext.y > 0x7fffffff || ext.z > 0x7fffffff)
+    throw std::invalid_argument("fill_f32: region extent exceeds 2^31 - 1");
   const Rect3 full = d.full_region();
+  if (!rect_inside(region, full))
+    throw std::invalid_argument("fill_f32: region " + region.str() +
+                                " is outside the allocation " + full.str());
   const Vec3 pos = region.lo - full.lo; // allocation coords
   const Pitched &pp = d.curr(qi);
   const int64_t off = pos.z * pp.plane() + pos.y * pp.pitch + pos.x * 4;

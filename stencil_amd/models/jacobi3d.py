@@ -93,7 +93,9 @@ class Jacobi3D:
         # buffer, so no translate fills a halo and the table swap moves
         # out of the graph (one swap after an odd run(n); see
         # csrc/src/jacobi.hip jacobi_graph_create; STENCIL_JAC_WRAP=0
-        # restores the translate graph). Halos are then STALE after
+        # restores the translate graph; so does a row length without
+        # room for the kernel's row extension, (X + 2r) % 64 == 0 unless
+        # the rect is aligned as it is). Halos are then STALE after
         # step()/run() until the next dd.exchange(): read_global over a
         # region that includes halo cells shows old values there. With a
         # non-periodic face the graph is [translate -> boundary fill ->
@@ -231,10 +233,13 @@ class Jacobi3D:
             # interior's row extension, so they go on stream 0 ORDERED
             # AFTER the interior kernel (their correct values must land
             # last); y/z slabs only touch rows the interior never writes
-            # and stay concurrent on the second compute stream
+            # and stay concurrent on the second compute stream. An x slab
+            # is one whose x range lies outside the interior's (slabs are
+            # `radius` wide: a width threshold would miss radius >= 3)
             for li in range(dd.num_local()):
+                ilo, ihi = self.interiors[li]
                 for blo, bhi in self.exteriors[li]:
-                    x_slab = ext_mode == 1 and (bhi[0] - blo[0]) <= 2
+                    x_slab = ext_mode == 1 and (bhi[0] <= ilo[0] or blo[0] >= ihi[0])
                     dd.backend.jacobi_step(
                         li, self.h.index, blo, bhi, self.compute_lo, self.compute_hi,
                         stream_id=0 if x_slab else 1,

@@ -670,10 +670,14 @@ class NativeBackend:
         self.domains[li].region_from_host(data, _vec3(pos), _vec3(ext), qi, to_next)
 
     def fill_f32(self, li: int, qi: int, region_lo: Vec, region_hi: Vec, value: float, next_buf: bool):
+        """ValueError (nothing launched) for a region outside the allocation"""
         _C.fill_f32(self.engine, li, qi, _rect3(region_lo, region_hi), value, next_buf)
 
     def jacobi_step(self, li: int, qi: int, region_lo: Vec, region_hi: Vec,
-                    c_lo: Vec, c_hi: Vec, stream_id: int = 0, extend_vec: bool = False):
+                    c_lo: Vec, c_hi: Vec, stream_id: int = 0, extend_vec: int = 0):
+        """one Jacobi step over the global box; extend_vec 0/1/2 as in
+        ops.hpp. ValueError (nothing launched) when the box plus its 1-cell
+        apron leaves the allocation."""
         _C.jacobi_step(self.engine, li, qi, _rect3(region_lo, region_hi), _rect3(c_lo, c_hi),
                        stream_id, extend_vec)
 
