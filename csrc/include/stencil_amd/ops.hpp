@@ -1,8 +1,11 @@
 // App compute ops (launched on a domain's compute stream).
 #pragma once
 
+#include <memory>
+
 #include "stencil_amd/core.hpp"
 #include "stencil_amd/engine.hpp"
+#include "stencil_amd/step_graph.hpp"
 
 namespace stencil_amd {
 
@@ -40,25 +43,54 @@ void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, flo
 // kernel alone, reading periodic neighbours from the far side of the
 // buffer (no translate, no in-graph swap; STENCIL_JAC_WRAP=0 turns it
 // off). Halos are then stale after a step until the next exchange.
-// jacobi_graph_is_wrap() tells which graph a handle holds.
-int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                            const Rect3 &computeRegion);
-void jacobi_graph_launch(int64_t handle, int64_t nSteps);
-void jacobi_graph_sync(int64_t handle);
-bool jacobi_graph_is_wrap(int64_t handle);
+// is_wrap() tells which of the two the graph is.
+// Ownership (all four graph classes below): the creator returns the only
+// owner; destroying it waits for its stream and frees its streams, events
+// and graph execs. A graph must be destroyed before the engine and domains
+// it was captured from.
+class JacobiStepGraph final : public ReplayGraph {
+public:
+  void launch(int64_t nSteps);
+  bool is_wrap() const { return wrap_; }
+
+private:
+  friend std::unique_ptr<JacobiStepGraph> jacobi_graph_create(ExchangeEngine &, int, int64_t,
+                                                              const Rect3 &, const Rect3 &);
+  JacobiStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                  const Rect3 &computeRegion);
+  hipGraphExec_t exec_[2] = {nullptr, nullptr};
+  // wrap graph: the stencil kernel alone; the device tables are flipped
+  // by launch(), not by a graph node
+  bool wrap_ = false;
+};
+std::unique_ptr<JacobiStepGraph> jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi,
+                                                     const Rect3 &region,
+                                                     const Rect3 &computeRegion);
 
 // Multi-rank whole-step graphs (see csrc/src/jacobi.hip): per parity,
 // A = [interior + translates + staged packs], B = [staged unpacks +
-// exterior + device swap]; the caller runs the cross-rank barrier in
-// between (RcclWire::barrier on jacobi_mr_graph_stream, or a host
-// barrier with stream syncs around it).
-int64_t jacobi_mr_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
-                               const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
-                               int extendVec);
-uintptr_t jacobi_mr_graph_stream(int64_t handle);
-void jacobi_mr_graph_pre(int64_t handle);
-void jacobi_mr_graph_post(int64_t handle);
-void jacobi_mr_graph_sync(int64_t handle);
+// exterior + device swap]; the caller runs pre() (A), the cross-rank
+// barrier (RcclWire::barrier on stream(), or a host barrier with sync()
+// around it), then post() (B).
+class JacobiMrStepGraph final : public ReplayGraph {
+public:
+  void pre();
+  void post();
+
+private:
+  friend std::unique_ptr<JacobiMrStepGraph>
+  jacobi_mr_graph_create(ExchangeEngine &, int, int64_t, const Rect3 &, const Rect3 &,
+                         const std::vector<Rect3> &, int);
+  JacobiMrStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
+                    const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
+                    int extendVec);
+  hipGraphExec_t execA_[2] = {nullptr, nullptr};
+  hipGraphExec_t execB_[2] = {nullptr, nullptr};
+};
+std::unique_ptr<JacobiMrStepGraph>
+jacobi_mr_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
+                       const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
+                       int extendVec);
 
 // Generic constant-coefficient linear stencil (csrc/src/stencil_op.hip):
 //   next[dstQ](p) = sum_k weights[k] * curr[srcQ](p + offsets[k])
@@ -145,23 +177,46 @@ void mhd_div_pass(ExchangeEngine &eng, int dom, const Rect3 &region, const MhdCo
 // Whole-substep hipGraphs for the world=1 single-domain astaroth shape:
 // per RK3 substep and buffer parity, [X1 translates -> div -> X2
 // translates -> scalar || momentum -> table swap] captured once;
-// mhd_graph_iter replays 3*nIters substep graphs (host mirrors flipped).
-int64_t mhd_graph_create(ExchangeEngine &eng, int dom, const Rect3 &region, double dt,
-                         const MhdCoeffs &cf);
-void mhd_graph_iter(int64_t handle, int64_t nIters = 1);
-void mhd_graph_sync(int64_t handle);
+// iter() replays 3*nIters substep graphs (host mirrors flipped).
+class MhdStepGraph final : public ReplayGraph {
+public:
+  void iter(int64_t nIters = 1);
+
+private:
+  friend std::unique_ptr<MhdStepGraph> mhd_graph_create(ExchangeEngine &, int, const Rect3 &,
+                                                        double, const MhdCoeffs &);
+  MhdStepGraph(ExchangeEngine &eng, int dom, const Rect3 &region, double dt,
+               const MhdCoeffs &cf);
+  hipGraphExec_t exec_[3][2] = {};
+};
+std::unique_ptr<MhdStepGraph> mhd_graph_create(ExchangeEngine &eng, int dom, const Rect3 &region,
+                                               double dt, const MhdCoeffs &cf);
 
 // Multi-rank substep graphs (see csrc/src/mhd.hip): per substep the
 // caller runs phase1 / barrier / phase2 / barrier / phase3 (barrier =
-// RcclWire::barrier on mhd_mr_graph_stream, or a host barrier with a
-// stream sync before it).
-int64_t mhd_mr_graph_create(ExchangeEngine &eng, int dom, const Rect3 &interior,
-                            const std::vector<Rect3> &exteriors, double dt, const MhdCoeffs &cf);
-uintptr_t mhd_mr_graph_stream(int64_t handle);
-void mhd_mr_phase1(int64_t handle);
-void mhd_mr_phase2(int64_t handle);
-void mhd_mr_phase3(int64_t handle);
-void mhd_mr_graph_sync(int64_t handle);
+// RcclWire::barrier on stream(), or a host barrier with a sync() before
+// it).
+class MhdMrStepGraph final : public ReplayGraph {
+public:
+  void phase1();
+  void phase2();
+  void phase3();
+
+private:
+  friend std::unique_ptr<MhdMrStepGraph> mhd_mr_graph_create(ExchangeEngine &, int, const Rect3 &,
+                                                            const std::vector<Rect3> &, double,
+                                                            const MhdCoeffs &);
+  MhdMrStepGraph(ExchangeEngine &eng, int dom, const Rect3 &interior,
+                 const std::vector<Rect3> &exteriors, double dt, const MhdCoeffs &cf);
+  hipGraphExec_t g1_[2] = {};
+  hipGraphExec_t g2_[3][2] = {};
+  hipGraphExec_t g3_[3][2] = {};
+  int substep_ = 0;
+};
+std::unique_ptr<MhdMrStepGraph> mhd_mr_graph_create(ExchangeEngine &eng, int dom,
+                                                    const Rect3 &interior,
+                                                    const std::vector<Rect3> &exteriors,
+                                                    double dt, const MhdCoeffs &cf);
 
 void mhd_substep(ExchangeEngine &eng, int dom, const Rect3 &region, int step, double dt,
                  const MhdCoeffs &cf, int streamId = 0);

@@ -415,6 +415,14 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("eng"), py::arg("dom"));
 
+  // Whole-step replay graphs: opaque owning objects. A live graph keeps its
+  // engine (and through it the domains) alive; dropping the last reference
+  // frees its streams, events and graph execs.
+  py::class_<JacobiStepGraph>(m, "JacobiStepGraph");
+  py::class_<JacobiMrStepGraph>(m, "JacobiMrStepGraph");
+  py::class_<MhdStepGraph>(m, "MhdStepGraph");
+  py::class_<MhdMrStepGraph>(m, "MhdMrStepGraph");
+  m.def("step_graphs_alive", &ReplayGraph::alive);
   m.def(
       "jacobi_graph_create",
       [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
@@ -423,10 +431,12 @@ PYBIND11_MODULE(_C, m) {
             [&] { return jacobi_graph_create(eng, dom, qi, region, computeRegion); });
       },
       py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("region"),
-      py::arg("compute_region"));
-  m.def("jacobi_graph_launch", &jacobi_graph_launch, py::arg("handle"), py::arg("n_steps") = 1);
-  m.def("jacobi_graph_sync", &jacobi_graph_sync);
-  m.def("jacobi_graph_is_wrap", &jacobi_graph_is_wrap);
+      py::arg("compute_region"), py::keep_alive<0, 1>());
+  m.def(
+      "jacobi_graph_launch", [](JacobiStepGraph &g, int64_t n) { g.launch(n); },
+      py::arg("handle"), py::arg("n_steps") = 1);
+  m.def("jacobi_graph_sync", [](JacobiStepGraph &g) { g.sync(); });
+  m.def("jacobi_graph_is_wrap", [](JacobiStepGraph &g) { return g.is_wrap(); });
   m.def(
       "jacobi_mr_graph_create",
       [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
@@ -438,22 +448,26 @@ PYBIND11_MODULE(_C, m) {
         });
       },
       py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("interior"),
-      py::arg("compute_region"), py::arg("exteriors"), py::arg("extend_vec") = 2);
-  m.def("jacobi_mr_graph_stream", &jacobi_mr_graph_stream);
-  m.def("jacobi_mr_graph_pre", &jacobi_mr_graph_pre);
-  m.def("jacobi_mr_graph_post", &jacobi_mr_graph_post);
-  m.def("jacobi_mr_graph_sync", &jacobi_mr_graph_sync);
+      py::arg("compute_region"), py::arg("exteriors"), py::arg("extend_vec") = 2,
+      py::keep_alive<0, 1>());
+  m.def("jacobi_mr_graph_stream", [](JacobiMrStepGraph &g) { return g.stream(); });
+  m.def("jacobi_mr_graph_pre", [](JacobiMrStepGraph &g) { g.pre(); });
+  m.def("jacobi_mr_graph_post", [](JacobiMrStepGraph &g) { g.post(); });
+  m.def("jacobi_mr_graph_sync", [](JacobiMrStepGraph &g) { g.sync(); });
   m.def("mhd_graph_create", &mhd_graph_create, py::arg("eng"), py::arg("dom"), py::arg("region"),
-        py::arg("dt"), py::arg("cf"));
-  m.def("mhd_graph_iter", &mhd_graph_iter, py::arg("handle"), py::arg("n_iters") = 1);
-  m.def("mhd_graph_sync", &mhd_graph_sync);
+        py::arg("dt"), py::arg("cf"), py::keep_alive<0, 1>());
+  m.def(
+      "mhd_graph_iter", [](MhdStepGraph &g, int64_t n) { g.iter(n); }, py::arg("handle"),
+      py::arg("n_iters") = 1);
+  m.def("mhd_graph_sync", [](MhdStepGraph &g) { g.sync(); });
   m.def("mhd_mr_graph_create", &mhd_mr_graph_create, py::arg("eng"), py::arg("dom"),
-        py::arg("interior"), py::arg("exteriors"), py::arg("dt"), py::arg("cf"));
-  m.def("mhd_mr_graph_stream", &mhd_mr_graph_stream);
-  m.def("mhd_mr_phase1", &mhd_mr_phase1);
-  m.def("mhd_mr_phase2", &mhd_mr_phase2);
-  m.def("mhd_mr_phase3", &mhd_mr_phase3);
-  m.def("mhd_mr_graph_sync", &mhd_mr_graph_sync);
+        py::arg("interior"), py::arg("exteriors"), py::arg("dt"), py::arg("cf"),
+        py::keep_alive<0, 1>());
+  m.def("mhd_mr_graph_stream", [](MhdMrStepGraph &g) { return g.stream(); });
+  m.def("mhd_mr_phase1", [](MhdMrStepGraph &g) { g.phase1(); });
+  m.def("mhd_mr_phase2", [](MhdMrStepGraph &g) { g.phase2(); });
+  m.def("mhd_mr_phase3", [](MhdMrStepGraph &g) { g.phase3(); });
+  m.def("mhd_mr_graph_sync", [](MhdMrStepGraph &g) { g.sync(); });
 
   py::class_<MhdCoeffs>(m, "MhdCoeffs")
       .def(py::init<>())

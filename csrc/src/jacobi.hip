@@ -658,22 +658,6 @@ void jacobi_step(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
 
 namespace {
 
-// One graph per buffer parity: the jacobi kernargs are baked per parity
-// (slot-indirecting the jacobi kernel itself was measured ~18% slower),
-// while the translate jobs stay slot-indirect and an in-graph
-// LocalDomain::enqueue_table_swap node flips the device tables.
-struct StepGraph {
-  hipStream_t stream = nullptr;
-  hipGraphExec_t exec[2] = {nullptr, nullptr};
-  int parity = 0;
-  ExchangeEngine *eng = nullptr;
-  int dom = 0;
-  // wrap graph: the stencil kernel alone; the device tables are flipped
-  // by jacobi_graph_launch, not by a graph node
-  bool wrap = false;
-};
-std::vector<std::unique_ptr<StepGraph>> g_stepGraphs;
-
 // The wrap-reading graph serves exactly the single-domain fully periodic
 // whole-domain step that launch_jacobi_on would give to
 // jacobi_kernel_v4_lds. STENCIL_JAC_WRAP=0 forces the translate graph (the
@@ -695,8 +679,22 @@ bool jacobi_wrap_eligible(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 
 
 } // namespace
 
-int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                            const Rect3 &computeRegion) {
+std::unique_ptr<JacobiStepGraph> jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi,
+                                                     const Rect3 &region,
+                                                     const Rect3 &computeRegion) {
+  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "jacobi_graph_create");
+  check_jacobi_region(d, region, "jacobi_graph_create");
+  return std::unique_ptr<JacobiStepGraph>(
+      new JacobiStepGraph(eng, dom, qi, region, computeRegion));
+}
+
+// One graph per buffer parity: the jacobi kernargs are baked per parity
+// (slot-indirecting the jacobi kernel itself was measured ~18% slower),
+// while the translate jobs stay slot-indirect and an in-graph
+// LocalDomain::enqueue_table_swap node flips the device tables.
+JacobiStepGraph::JacobiStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                                 const Rect3 &computeRegion)
+    : ReplayGraph(eng, dom) {
   // whole-step replay graph: [translate copy_batch -> boundary fill (if
   // any axis is non-periodic) -> full-region jacobi -> device-side table swap] captured once per buffer parity. Replay
   // costs one hipGraphLaunch (~5 us) instead of the ~0.25 ms of host
@@ -709,61 +707,44 @@ int64_t jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect
   // WRAP stencil kernel ALONE -- it reads the wrapped neighbour itself, no
   // translate fills a halo (59 us/step of strided face copies at 750^3)
   // and nothing in the graph reads the device pointer tables, so the
-  // table swap leaves the graph too (jacobi_graph_launch hoists it).
+  // table swap leaves the graph too (launch() hoists it).
   // Halos are STALE after steps taken on this path until the next
   // exchange(); interior cells are exact.
-  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "jacobi_graph_create");
-  check_jacobi_region(d, region, "jacobi_graph_create");
-  STENCIL_HIP(hipSetDevice(d.gpu()));
-  auto sg = std::make_unique<StepGraph>();
-  sg->eng = &eng;
-  sg->dom = dom;
-  sg->wrap = jacobi_wrap_eligible(eng, dom, qi, region, computeRegion);
-  STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking));
+  LocalDomain &d = domain();
+  wrap_ = jacobi_wrap_eligible(eng, dom, qi, region, computeRegion);
   for (int par = 0; par < 2; ++par) {
-    STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-    if (sg->wrap) {
-      launch_jacobi_on(d, qi, region, computeRegion, sg->stream, /*fullRectVec=*/1,
-                       /*wrap=*/true);
-    } else {
-      eng.launch_translates_plain_on((uintptr_t)sg->stream, 0);
-      // physical boundaries (no-op on a fully periodic domain): the fill
-      // reads halos the translates delivered, same stream so ordered
-      eng.launch_boundary_plain_on((uintptr_t)sg->stream, 0);
-      // the graph's region is the whole interior rect: pure-vector launch
-      // (scalar tail lanes measured ~10% of the kernel in the probe)
-      launch_jacobi_on(d, qi, region, computeRegion, sg->stream, /*fullRectVec=*/1);
-      d.enqueue_table_swap(sg->stream);
-    }
-    end_capture_instantiate(sg->stream, sg->exec[par]);
+    exec_[par] = capture([&] {
+      if (wrap_) {
+        launch_jacobi_on(d, qi, region, computeRegion, stream_, /*fullRectVec=*/1,
+                         /*wrap=*/true);
+      } else {
+        eng.launch_translates_plain_on((uintptr_t)stream_, 0);
+        // physical boundaries (no-op on a fully periodic domain): the fill
+        // reads halos the translates delivered, same stream so ordered
+        eng.launch_boundary_plain_on((uintptr_t)stream_, 0);
+        // the graph's region is the whole interior rect: pure-vector launch
+        // (scalar tail lanes measured ~10% of the kernel in the probe)
+        launch_jacobi_on(d, qi, region, computeRegion, stream_, /*fullRectVec=*/1);
+        d.enqueue_table_swap(stream_);
+      }
+    });
     d.swap(); // bake the other parity's kernarg pointers next round
   }
   // two swaps: host+device state is back where it started
-  g_stepGraphs.push_back(std::move(sg));
-  return (int64_t)g_stepGraphs.size() - 1;
 }
 
-void jacobi_graph_launch(int64_t handle, int64_t nSteps) {
-  StepGraph &sg = *g_stepGraphs.at(handle);
-  LocalDomain &d = sg.eng->domain(sg.dom);
-  STENCIL_HIP(hipSetDevice(d.gpu()));
+void JacobiStepGraph::launch(int64_t nSteps) {
+  LocalDomain &d = domain();
+  STENCIL_HIP(hipSetDevice(dev_));
   for (int64_t i = 0; i < nSteps; ++i) {
-    STENCIL_HIP(hipGraphLaunch(sg.exec[sg.parity], sg.stream));
-    sg.parity ^= 1;
+    STENCIL_HIP(hipGraphLaunch(exec_[parity_], stream_));
+    parity_ ^= 1;
     d.swap_host_only(); // in-graph kernel flips the device tables
   }
   // the wrap graph has no swap node (nothing in it reads the tables): an
   // even number of flips cancels, an odd one is ONE flip, enqueued behind
   // the replays so host and device state agree in stream order on return
-  if (sg.wrap && (nSteps & 1)) d.enqueue_table_swap(sg.stream);
-}
-
-bool jacobi_graph_is_wrap(int64_t handle) { return g_stepGraphs.at(handle)->wrap; }
-
-void jacobi_graph_sync(int64_t handle) {
-  StepGraph &sg = *g_stepGraphs.at(handle);
-  STENCIL_HIP(hipSetDevice(sg.eng->domain(sg.dom).gpu()));
-  STENCIL_HIP(hipStreamSynchronize(sg.stream));
+  if (wrap_ && (nSteps & 1)) d.enqueue_table_swap(stream_);
 }
 
 // Multi-rank whole-step graphs (one rank, one domain, cross-rank halos
@@ -780,76 +761,50 @@ void jacobi_graph_sync(int64_t handle) {
 // per run(n): the eager path's ~0.21 ms/step of host orchestration
 // (measured 0.989 vs 0.780 ms, profiles/r2/r2_gpu7_eager.log) collapses
 // to two graph launches + one collective post per step.
-namespace {
-struct MrStepGraph {
-  hipStream_t stream = nullptr;
-  hipGraphExec_t execA[2] = {nullptr, nullptr};
-  hipGraphExec_t execB[2] = {nullptr, nullptr};
-  int parity = 0;
-  ExchangeEngine *eng = nullptr;
-  int dom = 0;
-};
-std::vector<std::unique_ptr<MrStepGraph>> g_mrGraphs;
-} // namespace
-
-int64_t jacobi_mr_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
-                               const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
-                               int extendVec) {
+std::unique_ptr<JacobiMrStepGraph>
+jacobi_mr_graph_create(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
+                       const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
+                       int extendVec) {
   LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "jacobi_mr_graph_create");
   check_jacobi_region(d, interior, "jacobi_mr_graph_create");
   for (const Rect3 &box : exteriors) check_jacobi_region(d, box, "jacobi_mr_graph_create");
   if (extendVec < 0 || extendVec > 2)
     throw std::invalid_argument("jacobi_mr_graph_create: extend_vec must be 0, 1 or 2");
-  STENCIL_HIP(hipSetDevice(d.gpu()));
-  auto sg = std::make_unique<MrStepGraph>();
-  sg->eng = &eng;
-  sg->dom = dom;
-  STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking));
+  return std::unique_ptr<JacobiMrStepGraph>(
+      new JacobiMrStepGraph(eng, dom, qi, interior, computeRegion, exteriors, extendVec));
+}
+
+JacobiMrStepGraph::JacobiMrStepGraph(ExchangeEngine &eng, int dom, int64_t qi,
+                                     const Rect3 &interior, const Rect3 &computeRegion,
+                                     const std::vector<Rect3> &exteriors, int extendVec)
+    : ReplayGraph(eng, dom) {
+  LocalDomain &d = domain();
   for (int par = 0; par < 2; ++par) {
     // A: interior + outgoing halos
-    STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-    launch_jacobi_on(d, qi, interior, computeRegion, sg->stream, extendVec);
-    eng.launch_translates_plain_on((uintptr_t)sg->stream, 0);
-    eng.launch_packs_plain_on((uintptr_t)sg->stream, 1 + par); // staged parity
-    end_capture_instantiate(sg->stream, sg->execA[par]);
+    execA_[par] = capture([&] {
+      launch_jacobi_on(d, qi, interior, computeRegion, stream_, extendVec);
+      eng.launch_translates_plain_on((uintptr_t)stream_, 0);
+      eng.launch_packs_plain_on((uintptr_t)stream_, 1 + par); // staged parity
+    });
     // B: incoming halos + exterior + swap
-    STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-    eng.launch_unpacks_plain_on((uintptr_t)sg->stream, 1 + par);
-    for (const Rect3 &box : exteriors)
-      launch_jacobi_on(d, qi, box, computeRegion, sg->stream, /*fullRectVec=*/0);
-    d.enqueue_table_swap(sg->stream);
-    eng.enqueue_view_flips((uintptr_t)sg->stream);
-    end_capture_instantiate(sg->stream, sg->execB[par]);
+    execB_[par] = capture([&] {
+      eng.launch_unpacks_plain_on((uintptr_t)stream_, 1 + par);
+      for (const Rect3 &box : exteriors)
+        launch_jacobi_on(d, qi, box, computeRegion, stream_, /*fullRectVec=*/0);
+      d.enqueue_table_swap(stream_);
+      eng.enqueue_view_flips((uintptr_t)stream_);
+    });
     d.swap(); // bake the other parity's kernarg pointers next round
   }
-  g_mrGraphs.push_back(std::move(sg));
-  return (int64_t)g_mrGraphs.size() - 1;
 }
 
-uintptr_t jacobi_mr_graph_stream(int64_t handle) {
-  return (uintptr_t)g_mrGraphs.at(handle)->stream;
-}
+void JacobiMrStepGraph::pre() { launch(execA_[parity_]); }
 
-void jacobi_mr_graph_pre(int64_t handle) {
-  MrStepGraph &sg = *g_mrGraphs.at(handle);
-  STENCIL_HIP(hipSetDevice(sg.eng->domain(sg.dom).gpu()));
-  STENCIL_HIP(hipGraphLaunch(sg.execA[sg.parity], sg.stream));
-}
-
-void jacobi_mr_graph_post(int64_t handle) {
-  MrStepGraph &sg = *g_mrGraphs.at(handle);
-  LocalDomain &d = sg.eng->domain(sg.dom);
-  STENCIL_HIP(hipSetDevice(d.gpu()));
-  STENCIL_HIP(hipGraphLaunch(sg.execB[sg.parity], sg.stream));
-  sg.parity ^= 1;
-  d.swap_host_only(); // in-graph kernels flip the device state
-  sg.eng->flip_views_host_only();
-}
-
-void jacobi_mr_graph_sync(int64_t handle) {
-  MrStepGraph &sg = *g_mrGraphs.at(handle);
-  STENCIL_HIP(hipSetDevice(sg.eng->domain(sg.dom).gpu()));
-  STENCIL_HIP(hipStreamSynchronize(sg.stream));
+void JacobiMrStepGraph::post() {
+  launch(execB_[parity_]);
+  parity_ ^= 1;
+  domain().swap_host_only(); // in-graph kernels flip the device state
+  eng_.flip_views_host_only();
 }
 
 void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, float value,

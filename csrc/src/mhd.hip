@@ -416,8 +416,6 @@ void mhd_substep(ExchangeEngine &eng, int dom, const Rect3 &region, int step, do
                         eng.compute_stream(dom, 1 - streamId));
 }
 
-namespace {
-
 // Whole-substep replay graphs for the single-process single-domain MHD
 // path (the world=1 astaroth shape). Each RK3 substep s captures, per
 // buffer parity: [X1 translates (field halos, group 0) -> div pass ->
@@ -425,66 +423,44 @@ namespace {
 // second stream) -> device-side table swap]. The host gap measured
 // ~0.45 ms per substep at 256^3 (profiles/astaroth_256_kernel_stats.csv
 // GPU-busy vs wall); replay costs one hipGraphLaunch.
-struct MhdStepGraph {
-  hipStream_t stream = nullptr;  // capture/replay stream
-  hipStream_t stream2 = nullptr; // momentum fork
-  hipEvent_t evFork = nullptr, evJoin = nullptr;
-  hipGraphExec_t exec[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-  int parity = 0;
-  ExchangeEngine *eng = nullptr;
-  int dom = 0;
-};
-std::vector<std::unique_ptr<MhdStepGraph>> g_mhdGraphs;
+std::unique_ptr<MhdStepGraph> mhd_graph_create(ExchangeEngine &eng, int dom, const Rect3 &region,
+                                               double dt, const MhdCoeffs &cf) {
+  return std::unique_ptr<MhdStepGraph>(new MhdStepGraph(eng, dom, region, dt, cf));
+}
 
-} // namespace
-
-int64_t mhd_graph_create(ExchangeEngine &eng, int dom, const Rect3 &region, double dt,
-                         const MhdCoeffs &cf) {
-  LocalDomain &d = eng.domain(dom);
-  STENCIL_HIP(hipSetDevice(d.gpu()));
-  auto sg = std::make_unique<MhdStepGraph>();
-  sg->eng = &eng;
-  sg->dom = dom;
-  STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking));
-  STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream2, hipStreamNonBlocking));
-  STENCIL_HIP(hipEventCreateWithFlags(&sg->evFork, hipEventDisableTiming));
-  STENCIL_HIP(hipEventCreateWithFlags(&sg->evJoin, hipEventDisableTiming));
+MhdStepGraph::MhdStepGraph(ExchangeEngine &eng, int dom, const Rect3 &region, double dt,
+                           const MhdCoeffs &cf)
+    : ReplayGraph(eng, dom, /*nSide=*/1, /*nEvents=*/2) {
+  LocalDomain &d = domain();
+  const hipStream_t stream2 = side_[0]; // momentum fork
+  const hipEvent_t evFork = events_[0], evJoin = events_[1];
   for (int s = 0; s < 3; ++s) {
     for (int par = 0; par < 2; ++par) {
-      STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-      eng.launch_translates_plain_on((uintptr_t)sg->stream, 0); // X1: field halos
-      mhd_div_launch_on(d, region, cf, sg->stream);
-      eng.launch_translates_plain_on((uintptr_t)sg->stream, 1); // X2: div halos
-      STENCIL_HIP(hipEventRecord(sg->evFork, sg->stream));
-      STENCIL_HIP(hipStreamWaitEvent(sg->stream2, sg->evFork, 0));
-      mhd_substep_launch_on(d, region, s, dt, cf, sg->stream, sg->stream2);
-      STENCIL_HIP(hipEventRecord(sg->evJoin, sg->stream2));
-      STENCIL_HIP(hipStreamWaitEvent(sg->stream, sg->evJoin, 0));
-      d.enqueue_table_swap(sg->stream);
-      end_capture_instantiate(sg->stream, sg->exec[s][par]);
+      exec_[s][par] = capture([&] {
+        eng.launch_translates_plain_on((uintptr_t)stream_, 0); // X1: field halos
+        mhd_div_launch_on(d, region, cf, stream_);
+        eng.launch_translates_plain_on((uintptr_t)stream_, 1); // X2: div halos
+        STENCIL_HIP(hipEventRecord(evFork, stream_));
+        STENCIL_HIP(hipStreamWaitEvent(stream2, evFork, 0));
+        mhd_substep_launch_on(d, region, s, dt, cf, stream_, stream2);
+        STENCIL_HIP(hipEventRecord(evJoin, stream2));
+        STENCIL_HIP(hipStreamWaitEvent(stream_, evJoin, 0));
+        d.enqueue_table_swap(stream_);
+      });
       d.swap(); // bake the other parity next
     }
   }
-  g_mhdGraphs.push_back(std::move(sg));
-  return (int64_t)g_mhdGraphs.size() - 1;
 }
 
-void mhd_graph_iter(int64_t handle, int64_t nIters) {
-  MhdStepGraph &sg = *g_mhdGraphs.at(handle);
-  LocalDomain &d = sg.eng->domain(sg.dom);
-  STENCIL_HIP(hipSetDevice(d.gpu()));
+void MhdStepGraph::iter(int64_t nIters) {
+  LocalDomain &d = domain();
+  STENCIL_HIP(hipSetDevice(dev_));
   for (int64_t i = 0; i < nIters; ++i)
     for (int s = 0; s < 3; ++s) {
-      STENCIL_HIP(hipGraphLaunch(sg.exec[s][sg.parity], sg.stream));
-      sg.parity ^= 1;
+      STENCIL_HIP(hipGraphLaunch(exec_[s][parity_], stream_));
+      parity_ ^= 1;
       d.swap_host_only();
     }
-}
-
-void mhd_graph_sync(int64_t handle) {
-  MhdStepGraph &sg = *g_mhdGraphs.at(handle);
-  STENCIL_HIP(hipSetDevice(sg.eng->domain(sg.dom).gpu()));
-  STENCIL_HIP(hipStreamSynchronize(sg.stream));
 }
 
 // Multi-rank substep graphs (one rank, one domain, cross-rank halos via
@@ -497,110 +473,75 @@ void mhd_graph_sync(int64_t handle) {
 //   <barrier: every rank's div halos written>
 //   G3[s][par] = [staged unpacks g1 -> substep(exteriors) ->
 //                 device table swap + view flips]
-// The skew-safety argument is the jacobi one (jacobi_mr_graph_*): each
+// The skew-safety argument is the jacobi one (JacobiMrStepGraph): each
 // barrier bounds peers to one phase, staged buffers are double-buffered
 // by parity, and direct writes land in halo rings disjoint from locally
 // written compute cells.
-namespace {
-struct MhdMrGraph {
-  hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr;
-  hipEvent_t evF = nullptr, evJ2 = nullptr, evJ3 = nullptr;
-  hipGraphExec_t g1[2] = {nullptr, nullptr};
-  hipGraphExec_t g2[3][2] = {};
-  hipGraphExec_t g3[3][2] = {};
-  int parity = 0, substep = 0;
-  ExchangeEngine *eng = nullptr;
-  int dom = 0;
-};
-std::vector<std::unique_ptr<MhdMrGraph>> g_mhdMrGraphs;
-} // namespace
+std::unique_ptr<MhdMrStepGraph> mhd_mr_graph_create(ExchangeEngine &eng, int dom,
+                                                    const Rect3 &interior,
+                                                    const std::vector<Rect3> &exteriors,
+                                                    double dt, const MhdCoeffs &cf) {
+  return std::unique_ptr<MhdMrStepGraph>(
+      new MhdMrStepGraph(eng, dom, interior, exteriors, dt, cf));
+}
 
-int64_t mhd_mr_graph_create(ExchangeEngine &eng, int dom, const Rect3 &interior,
-                            const std::vector<Rect3> &exteriors, double dt, const MhdCoeffs &cf) {
-  LocalDomain &d = eng.domain(dom);
-  STENCIL_HIP(hipSetDevice(d.gpu()));
-  auto sg = std::make_unique<MhdMrGraph>();
-  sg->eng = &eng;
-  sg->dom = dom;
-  STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking));
-  STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream2, hipStreamNonBlocking));
-  STENCIL_HIP(hipStreamCreateWithFlags(&sg->stream3, hipStreamNonBlocking));
-  STENCIL_HIP(hipEventCreateWithFlags(&sg->evF, hipEventDisableTiming));
-  STENCIL_HIP(hipEventCreateWithFlags(&sg->evJ2, hipEventDisableTiming));
-  STENCIL_HIP(hipEventCreateWithFlags(&sg->evJ3, hipEventDisableTiming));
+MhdMrStepGraph::MhdMrStepGraph(ExchangeEngine &eng, int dom, const Rect3 &interior,
+                               const std::vector<Rect3> &exteriors, double dt,
+                               const MhdCoeffs &cf)
+    : ReplayGraph(eng, dom, /*nSide=*/2, /*nEvents=*/3) {
+  LocalDomain &d = domain();
+  const hipStream_t stream2 = side_[0], stream3 = side_[1];
+  const hipEvent_t evF = events_[0], evJ2 = events_[1], evJ3 = events_[2];
   for (int par = 0; par < 2; ++par) {
     // G1: div(interior) concurrent with the outgoing field halos
-    STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-    STENCIL_HIP(hipEventRecord(sg->evF, sg->stream));
-    STENCIL_HIP(hipStreamWaitEvent(sg->stream2, sg->evF, 0));
-    mhd_div_launch_on(d, interior, cf, sg->stream);
-    eng.launch_translates_plain_on((uintptr_t)sg->stream2, 0);
-    eng.launch_packs_plain_on((uintptr_t)sg->stream2, 1 + par);
-    STENCIL_HIP(hipEventRecord(sg->evJ2, sg->stream2));
-    STENCIL_HIP(hipStreamWaitEvent(sg->stream, sg->evJ2, 0));
-    end_capture_instantiate(sg->stream, sg->g1[par]);
+    g1_[par] = capture([&] {
+      STENCIL_HIP(hipEventRecord(evF, stream_));
+      STENCIL_HIP(hipStreamWaitEvent(stream2, evF, 0));
+      mhd_div_launch_on(d, interior, cf, stream_);
+      eng.launch_translates_plain_on((uintptr_t)stream2, 0);
+      eng.launch_packs_plain_on((uintptr_t)stream2, 1 + par);
+      STENCIL_HIP(hipEventRecord(evJ2, stream2));
+      STENCIL_HIP(hipStreamWaitEvent(stream_, evJ2, 0));
+    });
     for (int s = 0; s < 3; ++s) {
       // G2: incoming field halos -> div(ext) -> div halos out || interior
-      STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-      eng.launch_unpacks_plain_on((uintptr_t)sg->stream, 1 + par);
-      for (const Rect3 &box : exteriors) mhd_div_launch_on(d, box, cf, sg->stream);
-      STENCIL_HIP(hipEventRecord(sg->evF, sg->stream));
-      STENCIL_HIP(hipStreamWaitEvent(sg->stream2, sg->evF, 0));
-      STENCIL_HIP(hipStreamWaitEvent(sg->stream3, sg->evF, 0));
-      eng.launch_translates_plain_on((uintptr_t)sg->stream, 1);
-      eng.launch_packs_plain_on((uintptr_t)sg->stream, 4 + par); // 3*1+1+par
-      mhd_substep_launch_on(d, interior, s, dt, cf, sg->stream2, sg->stream3);
-      STENCIL_HIP(hipEventRecord(sg->evJ2, sg->stream2));
-      STENCIL_HIP(hipEventRecord(sg->evJ3, sg->stream3));
-      STENCIL_HIP(hipStreamWaitEvent(sg->stream, sg->evJ2, 0));
-      STENCIL_HIP(hipStreamWaitEvent(sg->stream, sg->evJ3, 0));
-      end_capture_instantiate(sg->stream, sg->g2[s][par]);
+      g2_[s][par] = capture([&] {
+        eng.launch_unpacks_plain_on((uintptr_t)stream_, 1 + par);
+        for (const Rect3 &box : exteriors) mhd_div_launch_on(d, box, cf, stream_);
+        STENCIL_HIP(hipEventRecord(evF, stream_));
+        STENCIL_HIP(hipStreamWaitEvent(stream2, evF, 0));
+        STENCIL_HIP(hipStreamWaitEvent(stream3, evF, 0));
+        eng.launch_translates_plain_on((uintptr_t)stream_, 1);
+        eng.launch_packs_plain_on((uintptr_t)stream_, 4 + par); // 3*1+1+par
+        mhd_substep_launch_on(d, interior, s, dt, cf, stream2, stream3);
+        STENCIL_HIP(hipEventRecord(evJ2, stream2));
+        STENCIL_HIP(hipEventRecord(evJ3, stream3));
+        STENCIL_HIP(hipStreamWaitEvent(stream_, evJ2, 0));
+        STENCIL_HIP(hipStreamWaitEvent(stream_, evJ3, 0));
+      });
       // G3: incoming div halos -> exterior shells -> swap
-      STENCIL_HIP(hipStreamBeginCapture(sg->stream, hipStreamCaptureModeThreadLocal));
-      eng.launch_unpacks_plain_on((uintptr_t)sg->stream, 4 + par);
-      for (const Rect3 &box : exteriors)
-        mhd_substep_launch_on(d, box, s, dt, cf, sg->stream, sg->stream);
-      d.enqueue_table_swap(sg->stream);
-      eng.enqueue_view_flips((uintptr_t)sg->stream);
-      end_capture_instantiate(sg->stream, sg->g3[s][par]);
+      g3_[s][par] = capture([&] {
+        eng.launch_unpacks_plain_on((uintptr_t)stream_, 4 + par);
+        for (const Rect3 &box : exteriors)
+          mhd_substep_launch_on(d, box, s, dt, cf, stream_, stream_);
+        d.enqueue_table_swap(stream_);
+        eng.enqueue_view_flips((uintptr_t)stream_);
+      });
     }
     d.swap(); // bake the other parity's kernarg pointers next round
   }
-  g_mhdMrGraphs.push_back(std::move(sg));
-  return (int64_t)g_mhdMrGraphs.size() - 1;
 }
 
-uintptr_t mhd_mr_graph_stream(int64_t handle) {
-  return (uintptr_t)g_mhdMrGraphs.at(handle)->stream;
-}
+void MhdMrStepGraph::phase1() { launch(g1_[parity_]); }
 
-void mhd_mr_phase1(int64_t handle) {
-  MhdMrGraph &sg = *g_mhdMrGraphs.at(handle);
-  STENCIL_HIP(hipSetDevice(sg.eng->domain(sg.dom).gpu()));
-  STENCIL_HIP(hipGraphLaunch(sg.g1[sg.parity], sg.stream));
-}
+void MhdMrStepGraph::phase2() { launch(g2_[substep_][parity_]); }
 
-void mhd_mr_phase2(int64_t handle) {
-  MhdMrGraph &sg = *g_mhdMrGraphs.at(handle);
-  STENCIL_HIP(hipSetDevice(sg.eng->domain(sg.dom).gpu()));
-  STENCIL_HIP(hipGraphLaunch(sg.g2[sg.substep][sg.parity], sg.stream));
-}
-
-void mhd_mr_phase3(int64_t handle) {
-  MhdMrGraph &sg = *g_mhdMrGraphs.at(handle);
-  LocalDomain &d = sg.eng->domain(sg.dom);
-  STENCIL_HIP(hipSetDevice(d.gpu()));
-  STENCIL_HIP(hipGraphLaunch(sg.g3[sg.substep][sg.parity], sg.stream));
-  sg.substep = (sg.substep + 1) % 3;
-  sg.parity ^= 1;
-  d.swap_host_only(); // in-graph kernels flip the device state
-  sg.eng->flip_views_host_only();
-}
-
-void mhd_mr_graph_sync(int64_t handle) {
-  MhdMrGraph &sg = *g_mhdMrGraphs.at(handle);
-  STENCIL_HIP(hipSetDevice(sg.eng->domain(sg.dom).gpu()));
-  STENCIL_HIP(hipStreamSynchronize(sg.stream));
+void MhdMrStepGraph::phase3() {
+  launch(g3_[substep_][parity_]);
+  substep_ = (substep_ + 1) % 3;
+  parity_ ^= 1;
+  domain().swap_host_only(); // in-graph kernels flip the device state
+  eng_.flip_views_host_only();
 }
 
 } // namespace stencil_amd

@@ -291,6 +291,8 @@ class Astaroth:
                 self._mr_iter()
                 return
             # parity cannot be resynced after an eager substep; degrade
+            # (dropping the last reference frees the graph's streams,
+            # events and graph execs)
             self._mr_graph = None
         for s in range(3):
             self._substep(s, dt, compute, overlap)

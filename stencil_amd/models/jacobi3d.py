@@ -179,7 +179,8 @@ class Jacobi3D:
                 self._mr_step()
                 return
             # the graph's parity cannot be resynced once an eager step
-            # interleaves; degrade one-way to the eager path
+            # interleaves; degrade one-way to the eager path (dropping the
+            # last reference frees the graph's streams and graph execs)
             self._mr_graph = None
         self._eager_step(overlap)
 

@@ -745,15 +745,16 @@ class NativeBackend:
         return out
 
     def jacobi_graph_create(self, li: int, qi: int, region_lo: Vec, region_hi: Vec,
-                            c_lo: Vec, c_hi: Vec) -> int:
+                            c_lo: Vec, c_hi: Vec) -> "_C.JacobiStepGraph":
         """whole-step replay graph (single-process single-domain path);
-        see csrc/src/jacobi.hip jacobi_graph_create"""
+        see csrc/src/jacobi.hip jacobi_graph_create. The returned object
+        owns the graph and keeps the engine alive; dropping it frees it."""
         return _C.jacobi_graph_create(self.engine, li, qi, _rect3(region_lo, region_hi),
                                       _rect3(c_lo, c_hi))
 
-    def jacobi_graph_step(self, handle: int, n: int = 1):
-        _C.jacobi_graph_launch(handle, n)
-        _C.jacobi_graph_sync(handle)
+    def jacobi_graph_step(self, graph: "_C.JacobiStepGraph", n: int = 1):
+        _C.jacobi_graph_launch(graph, n)
+        _C.jacobi_graph_sync(graph)
 
     def sync_compute(self):
         self.engine.sync_compute()

@@ -256,6 +256,7 @@ def test_validation_launches_nothing():
         (lo, (hi[0], hi[1], hi[2] + 1)),
         ((lo[0] + 100, lo[1], lo[2]), (hi[0] + 100, hi[1], hi[2])),
     ]
+    graphs_before = _C.step_graphs_alive()
     for rlo, rhi in bad_regions:
         for mode in MODES:
             with pytest.raises(ValueError):
@@ -275,6 +276,8 @@ def test_validation_launches_nothing():
     with pytest.raises(ValueError):
         _C.jacobi_mr_graph_create(b.engine, 0, h.index, rect(flo, fhi), rect((0, 0, 0), size),
                                   [], extend_vec=2)
+    # a refused creation leaves no graph object behind
+    assert _C.step_graphs_alive() == graphs_before
     # fill_f32: the region itself must be inside the full region
     for next_buf in (False, True):
         for rlo, rhi in (

@@ -113,6 +113,14 @@ def _jacobi_worker(rank, world, port, q, use_ipc, step_graph=True):
         for li in range(app.dd.num_local()):
             lo, hi = app.dd.local_rect(li)
             out.append((lo, hi, app.dd.read_global(li, lo, hi, app.h)))
+        # the app owns its step graph: nothing of it survives the app
+        import gc
+
+        from stencil_amd import _C
+
+        del app
+        gc.collect()
+        assert _C.step_graphs_alive() == 0
         dist.destroy_process_group()
         q.put((rank, "ok", out))
     except Exception as e:  # pragma: no cover

@@ -54,6 +54,14 @@ def _worker(rank, world, port, q, step_graph=True):
                 np.testing.assert_allclose(
                     got, want, rtol=1e-9, atol=1e-12, err_msg=f"{name} li={li} rank={rank}"
                 )
+        # the app owns its substep graphs: nothing of them survives the app
+        import gc
+
+        from stencil_amd import _C
+
+        del app
+        gc.collect()
+        assert _C.step_graphs_alive() == 0
         dist.destroy_process_group()
         q.put((rank, "ok"))
     except Exception as e:  # pragma: no cover
