@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Conjugate-gradient benchmark: (sigma I - laplacian) x = b on a size^3
-grid with Poisson3D, exactly --iters iterations (tol = 0).
+grid with Poisson3D, exactly --iters iterations (--tol 0, the default), or
+solved to --tol T > 0 with at most --iters iterations: the record then
+holds iterations, converged, solve_ms and levels as well. --precond mg
+preconditions with the geometric multigrid V-cycle and adds precond_ms, the
+host wall time per level of one cycle (mg_level_ms) and coarse_share, the
+part of a cycle spent on levels >= 1.
 
 Prints one JSON line: ms_per_iter, gcells_per_s and the host wall time per
 iteration of the three phases (each ends in a host sync):
@@ -10,7 +15,9 @@ iteration of the three phases (each ends in a host sync):
 --kernels N adds a kernel-only window per vector kernel (N launches
 enqueued, one sync) with its effective bandwidth, one element read or
 written counting as one pass: dot 2, cg_update 6, the p update 3; and the
-cost of one empty host sync of the compute stream.
+cost of one empty host sync of the compute stream. With --precond mg also
+axpbypcz 4, grid_restrict 2 + 1/8 and grid_prolong_add 2 + 1/8 passes over
+the fine grid.
 """
 import argparse
 import json
@@ -48,13 +55,17 @@ def main():
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--kernels", type=int, default=0, metavar="N",
                     help="also time N back-to-back launches of each vector kernel")
+    ap.add_argument("--precond", default="none", choices=["none", "mg"])
+    ap.add_argument("--tol", type=float, default=0.0,
+                    help="0: exactly --iters iterations; > 0: solve to this tolerance")
     args = ap.parse_args()
 
     dtype = np.float32 if args.dtype == "f32" else np.float64
     gpus = list(range(args.gpus)) if args.backend == "native" else [0] * args.gpus
     size = (args.size,) * 3
     app = Poisson3D(size, order=args.order, dtype=dtype, sigma=args.sigma, backend=args.backend,
-                    gpus=gpus, boundary=_BOUNDARIES[args.boundary])
+                    gpus=gpus, boundary=_BOUNDARIES[args.boundary],
+                    preconditioner="multigrid" if args.precond == "mg" else None)
     app.realize()
     dd = app.dd
     rng = np.random.default_rng(0)
@@ -67,8 +78,10 @@ def main():
     if args.warmup:
         app.solve(tol=0.0, max_iter=args.warmup, overlap=overlap)
     dd.backend.sync()
+    if app.mg is not None:
+        app.mg.reset_times()
     t0 = time.perf_counter()
-    res = app.solve(tol=0.0, max_iter=args.iters, overlap=overlap)
+    res = app.solve(tol=args.tol, max_iter=args.iters, overlap=overlap)
     dd.backend.sync()
     dt = time.perf_counter() - t0
     n = max(res.iterations, 1)
@@ -93,20 +106,33 @@ def main():
         "operator_ms": ph["operator"] / n * 1e3,
         "dot_ms": ph["dot"] / n * 1e3,
         "update_ms": ph["update"] / n * 1e3,
+        "precond": args.precond,
+        "tol": args.tol,
     }
+    if args.tol > 0:
+        out["iterations"] = res.iterations
+        out["converged"] = res.converged
+        out["solve_ms"] = dt * 1e3
+        out["levels"] = [list(lv) for lv in app.mg.levels] if app.mg is not None else None
+    if app.mg is not None:
+        cycles = res.iterations + 1  # one per iteration and the first z = M r
+        level_ms = [t / cycles * 1e3 for t in app.mg.phase_times.values()]
+        out["precond_ms"] = ph["precond"] / n * 1e3
+        out["mg_level_ms"] = level_ms
+        out["coarse_share"] = sum(level_ms[1:]) / sum(level_ms)
 
     if args.kernels:
         k = args.kernels
         es = np.dtype(dtype).itemsize
         x, r, p = app.x, app.r, app.p
 
-        def window(fn):
+        def window(fn, sync=dd.backend.sync):
             fn()
-            dd.backend.sync()
+            sync()
             t = time.perf_counter()
             for _ in range(k):
                 fn()
-            dd.backend.sync()
+            sync()
             return (time.perf_counter() - t) / k * 1e3
 
         def report(name, passes, t_ms):
@@ -118,6 +144,19 @@ def main():
         # the reductions wait for their value: a window of k synchronous calls
         report("dot", 2, window(lambda: dd.dot(p, sa.Next(p))))
         report("cg_update", 6, window(lambda: dd.cg_update(1e-30, x, p, r)))
+        if app.mg is not None:
+            z, top = app.z, app.mg._levels[0]
+            coarse = app.mg._levels[1]
+            report("axpbypcz", 4,
+                   window(lambda: dd.axpbypcz(1.0, z, 1e-30, r, -1e-30, sa.Next(z), out=z)))
+
+            # each transfer call syncs its source side first, an idle stream
+            # here; the restriction runs on the coarse domain's stream
+            report("grid_restrict", 2.125,
+                   window(lambda: top.transfer.restrict(1.0, r, -1.0, sa.Next(z), coarse.f),
+                          sync=coarse.dd.backend.sync))
+            report("grid_prolong_add", 2.125,
+                   window(lambda: top.transfer.prolong_add(coarse.f, z)))
         t = time.perf_counter()
         for _ in range(k):
             dd.backend.sync_compute()

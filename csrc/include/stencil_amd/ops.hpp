@@ -146,6 +146,13 @@ void field_dot_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_
 void field_axpby(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
                  int64_t y, bool yNext, int64_t out, bool outNext, const Rect3 &region,
                  int streamId = 0);
+// out = alpha * x + beta * y + gamma * z, the three-operand form of
+// field_axpby (4 passes where two axpby calls take 6): the relaxation
+// update e += w (f - A e) of the multigrid smoother. out may be the buffer
+// of any input.
+void field_axpbypcz(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                    double beta, int64_t y, bool yNext, double gamma, int64_t z, bool zNext,
+                    int64_t out, bool outNext, const Rect3 &region, int streamId = 0);
 // fused conjugate-gradient update, one pass instead of three:
 //   curr[x] += alpha * curr[p];  curr[r] -= alpha * next[p]
 // returning sum r_new^2 (fp64 accumulation of the rounded r_new). next[p]
@@ -156,6 +163,35 @@ void cg_update_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int6
                      const Rect3 &region, int streamId = 0);
 // wait for the reduction begun on `dom` and return its value
 double reduction_end(ExchangeEngine &eng, int dom);
+
+// Grid transfer between a fine and a coarse local domain on cell-centred
+// 2:1 coarsening (csrc/src/grid_transfer.hip): coarse cell c has the 8 fine
+// children 2c + {0,1}^3, all coordinates global. The two domains may belong
+// to different engines but sit on one device; the kernel is enqueued on
+// compute_stream(dom, streamId) of the DESTINATION engine, and the caller
+// orders it behind the source engine's work (sync_compute). float32 /
+// float64 quantities, all operands of one type; an operand is (quantity,
+// nextBuf). The contract of the vector operations holds: nothing outside
+// the region is written in any buffer, and no cell outside it (for the
+// restriction: outside the children of the region) is loaded, so halos may
+// hold NaN. Both throw std::invalid_argument, and launch nothing, for an
+// unknown domain or quantity, an element size other than 4 or 8 or mixed
+// element sizes, a coarse region outside the coarse full_region() or whose
+// doubled box [2 lo, 2 hi) leaves the fine full_region(), and domains on
+// different devices. An empty region is a no-op.
+//
+// out(c) = 0.125 * sum over the children p of c of (alpha a(p) + beta b(p)),
+// in the quantity's type (alpha, beta rounded to it once; summation order
+// and FMA contraction unspecified). Two operands, so that a residual
+// f - A e is restricted without being written out first.
+void grid_restrict(ExchangeEngine &fine, int fdom, double alpha, int64_t a, bool aNext,
+                   double beta, int64_t b, bool bNext, ExchangeEngine &coarse, int cdom,
+                   int64_t out, bool outNext, const Rect3 &coarseRegion, int streamId = 0);
+// dst(p) += src(p >> 1) for every fine cell p of [2 lo, 2 hi): piecewise-
+// constant injection, 8 x the transpose of the restriction above.
+void grid_prolong_add(ExchangeEngine &coarse, int cdom, int64_t src, bool srcNext,
+                      ExchangeEngine &fine, int fdom, int64_t dst, bool dstNext,
+                      const Rect3 &coarseRegion, int streamId = 0);
 
 // physical coefficients of the MHD solver (see csrc/src/mhd.hip)
 struct MhdCoeffs {

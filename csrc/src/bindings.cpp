@@ -390,6 +390,50 @@ PYBIND11_MODULE(_C, m) {
       py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"), py::arg("out_next"),
       py::arg("region"), py::arg("stream_id") = 0);
   m.def(
+      "field_axpbypcz",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                     double beta, int64_t y, bool yNext, double gamma, int64_t z, bool zNext,
+                     int64_t out, bool outNext, const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_axpbypcz(eng, dom, alpha, x, xNext, beta, y, yNext, gamma, z, zNext, out, outNext,
+                         region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
+      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("gamma"), py::arg("z"),
+      py::arg("z_next"), py::arg("out"), py::arg("out_next"), py::arg("region"),
+      py::arg("stream_id") = 0);
+  // grid transfer (csrc/src/grid_transfer.hip)
+  m.def(
+      "grid_restrict",
+      [value_errors](ExchangeEngine &fine, int fdom, double alpha, int64_t a, bool aNext,
+                     double beta, int64_t b, bool bNext, ExchangeEngine &coarse, int cdom,
+                     int64_t out, bool outNext, const Rect3 &coarseRegion, int streamId) {
+        value_errors([&] {
+          grid_restrict(fine, fdom, alpha, a, aNext, beta, b, bNext, coarse, cdom, out, outNext,
+                        coarseRegion, streamId);
+          return 0;
+        });
+      },
+      py::arg("fine"), py::arg("fdom"), py::arg("alpha"), py::arg("a"), py::arg("a_next"),
+      py::arg("beta"), py::arg("b"), py::arg("b_next"), py::arg("coarse"), py::arg("cdom"),
+      py::arg("out"), py::arg("out_next"), py::arg("coarse_region"), py::arg("stream_id") = 0);
+  m.def(
+      "grid_prolong_add",
+      [value_errors](ExchangeEngine &coarse, int cdom, int64_t src, bool srcNext,
+                     ExchangeEngine &fine, int fdom, int64_t dst, bool dstNext,
+                     const Rect3 &coarseRegion, int streamId) {
+        value_errors([&] {
+          grid_prolong_add(coarse, cdom, src, srcNext, fine, fdom, dst, dstNext, coarseRegion,
+                           streamId);
+          return 0;
+        });
+      },
+      py::arg("coarse"), py::arg("cdom"), py::arg("src"), py::arg("src_next"), py::arg("fine"),
+      py::arg("fdom"), py::arg("dst"), py::arg("dst_next"), py::arg("coarse_region"),
+      py::arg("stream_id") = 0);
+  m.def(
       "cg_update",
       [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
                      const Rect3 &region, int streamId) {

@@ -1,5 +1,6 @@
 // Vector operations on pitched quantities for gfx950: the inner product,
-// out = alpha x + beta y, and the fused conjugate-gradient update. Pure
+// out = alpha x + beta y, out = alpha x + beta y + gamma z, and the fused
+// conjugate-gradient update. Pure
 // streaming kernels: every cell of the region is read (and written) once.
 //
 // Contract (the stencil operator's): nothing outside `region` is written
@@ -161,6 +162,16 @@ template <typename T> struct AxpbyF {
   }
 };
 
+template <typename T> struct AxpbypczF {
+  const char *x, *y, *z;
+  char *out;
+  T alpha, beta, gamma;
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vx = *(const V *)(x + off), vy = *(const V *)(y + off), vz = *(const V *)(z + off);
+    *(V *)(out + off) = alpha * vx + beta * vy + gamma * vz;
+  }
+};
+
 template <typename T> struct CgF {
   char *x, *r;
   const char *p, *ap;
@@ -188,6 +199,14 @@ template <typename T, bool STRIPS>
 __global__ void __launch_bounds__(256)
     axpby_kernel(Geom g, const char *x, const char *y, char *out, T alpha, T beta) {
   AxpbyF<T> f{x, y, out, alpha, beta};
+  walk<T, STRIPS>(g, f);
+}
+
+template <typename T, bool STRIPS>
+__global__ void __launch_bounds__(256)
+    axpbypcz_kernel(Geom g, const char *x, const char *y, const char *z, char *out, T alpha,
+                    T beta, T gamma) {
+  AxpbypczF<T> f{x, y, z, out, alpha, beta, gamma};
   walk<T, STRIPS>(g, f);
 }
 
@@ -412,6 +431,24 @@ void field_axpby(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNe
   } else {
     VEC_OPS_LAUNCH(double, l, axpby_kernel, stream, l.g, (const char *)l.ptr[0],
                    (const char *)l.ptr[1], l.ptr[2], alpha, beta);
+  }
+}
+
+void field_axpbypcz(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                    double beta, int64_t y, bool yNext, double gamma, int64_t z, bool zNext,
+                    int64_t out, bool outNext, const Rect3 &region, int streamId) {
+  const Launch l = plan_launch("field_axpbypcz", eng, dom,
+                               {{x, xNext}, {y, yNext}, {z, zNext}, {out, outNext}}, region);
+  if (l.empty) return;
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  if (l.es == 4) {
+    const float al = (float)alpha, be = (float)beta, ga = (float)gamma; // rounded once
+    VEC_OPS_LAUNCH(float, l, axpbypcz_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], (const char *)l.ptr[2], l.ptr[3], al, be, ga);
+  } else {
+    VEC_OPS_LAUNCH(double, l, axpbypcz_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], (const char *)l.ptr[2], l.ptr[3], alpha, beta, gamma);
   }
 }
 

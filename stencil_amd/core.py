@@ -472,6 +472,16 @@ class DistributedDomain:
         boxes = self._vector_boxes("axpby", where)
         self.backend.field_axpby(boxes, float(alpha), qx, nx, float(beta), qy, ny, qo, no)
 
+    def axpbypcz(self, alpha: float, x, beta: float, y, gamma: float, z, out, where="all"):
+        """out = alpha * x + beta * y + gamma * z, the three-operand axpby
+        (one 4-pass kernel): the relaxation update e += w (f - A e) of the
+        multigrid smoother. out may be the buffer of any input. Enqueued on
+        compute stream 0 like axpby."""
+        (qx, nx), (qy, ny), (qz, nz), (qo, no) = self._vector_operands("axpbypcz", [x, y, z, out])
+        boxes = self._vector_boxes("axpbypcz", where)
+        self.backend.field_axpbypcz(boxes, float(alpha), qx, nx, float(beta), qy, ny,
+                                    float(gamma), qz, nz, qo, no)
+
     def cg_update(self, alpha: float, x, p, r) -> float:
         """the fused conjugate-gradient update over every local_rect:
         curr[x] += alpha * curr[p]; curr[r] -= alpha * next[p] (where

@@ -731,6 +731,39 @@ class NativeBackend:
             _C.field_axpby(self.engine, li, alpha, x, x_next, beta, y, y_next, out, out_next,
                            _rect3(lo, hi), stream_id)
 
+    def field_axpbypcz(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
+                       y_next: bool, gamma: float, z: int, z_next: bool, out: int,
+                       out_next: bool, stream_id: int = 0):
+        """out = alpha * x + beta * y + gamma * z over each local domain's
+        box; out may alias any input. Enqueued, not awaited."""
+        for li, (lo, hi) in enumerate(boxes):
+            _C.field_axpbypcz(self.engine, li, alpha, x, x_next, beta, y, y_next, gamma, z, z_next,
+                              out, out_next, _rect3(lo, hi), stream_id)
+
+    # ---- grid transfer (csrc/src/grid_transfer.hip) ----
+    # self is the DESTINATION backend: its compute stream carries the kernel.
+    # Boxes are coarse global boxes; the caller has synced the source side.
+    def grid_restrict(self, fine: "NativeBackend", fli: int, alpha: float, a: int, a_next: bool,
+                      beta: float, b: int, b_next: bool, cli: int, out: int, out_next: bool,
+                      lo: Vec, hi: Vec, stream_id: int = 0):
+        """coarse out(c) = mean over the 8 children of alpha a + beta b, for
+        the coarse cells c of [lo, hi) of this backend's local domain cli;
+        a and b live in local domain fli of `fine`"""
+        _C.grid_restrict(fine.engine, fli, alpha, a, a_next, beta, b, b_next, self.engine, cli,
+                         out, out_next, _rect3(lo, hi), stream_id)
+
+    def grid_prolong_add(self, coarse: "NativeBackend", cli: int, src: int, src_next: bool,
+                         fli: int, dst: int, dst_next: bool, lo: Vec, hi: Vec,
+                         stream_id: int = 0):
+        """fine dst(p) += src(p >> 1) for the fine cells of [2 lo, 2 hi) of
+        this backend's local domain fli; src lives in local domain cli of
+        `coarse`"""
+        _C.grid_prolong_add(coarse.engine, cli, src, src_next, self.engine, fli, dst, dst_next,
+                            _rect3(lo, hi), stream_id)
+
+    def device_of(self, li: int) -> int:
+        return self.domains[li].gpu()
+
     def cg_update(self, boxes, alpha: float, x: int, p: int, r: int,
                   stream_id: int = 0) -> List[float]:
         """fused CG update per local domain: curr[x] += alpha * curr[p];

@@ -16,6 +16,16 @@ next buffer of `p`, where apply_stencil leaves it, so four quantities
              stop if rr_new <= tol^2 * bb
              p = r + (rr_new / rr) * p ;  rr = rr_new
 
+With a preconditioner M (any object with apply(r, z) leaving z = M r, M
+symmetric positive definite; solvers/multigrid.py) and a fifth quantity z:
+
+    z = M r; p = z; rz = dot(r, z)
+    repeat:  next[p] = A p;  alpha = rz / dot(p, Next(p))
+             rr_new = cg_update(alpha, x, p, r);  stop if rr_new <= tol^2 * bb
+             z = M r; rz_new = dot(r, z);  p = z + (rz_new / rz) * p
+
+Without one the code path is the loop above, unchanged.
+
 Boundary conditions. CG needs A symmetric, and linear and homogeneous in
 the field: PERIODIC, FIXED(0), MIRROR and ANTIMIRROR qualify (for star
 stencils: `u . A v == v . A u` was checked to rounding for the Laplacians
@@ -56,65 +66,92 @@ class CGResult:
 _FACES = ("x-", "x+", "y-", "y+", "z-", "z+")
 
 
+def check_operator(who: str, dd: DistributedDomain, operator: Stencil):
+    """ValueError unless the stencil is symmetric and dd's radius covers it"""
+    if not operator.is_symmetric():
+        raise ValueError(f"{who}: the stencil is not symmetric (w(o) != w(-o))")
+    need = operator.radius()
+    for dz in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                if (dx, dy, dz) != (0, 0, 0) and dd.radius.dir(dx, dy, dz) < need.dir(dx, dy, dz):
+                    raise ValueError(
+                        f"{who}: the domain's radius {dd.radius.dir(dx, dy, dz)} in "
+                        f"direction {(dx, dy, dz)} does not cover the stencil's "
+                        f"{need.dir(dx, dy, dz)}"
+                    )
+
+
+def check_boundary(who: str, dd: DistributedDomain, handles):
+    """ValueError unless every non-periodic face of the given quantities is
+    FIXED(0), MIRROR or ANTIMIRROR"""
+    spec = dd.boundary
+    if spec is None:
+        return
+    for h in handles:
+        for a in range(3):
+            if spec.periodic[a]:
+                continue
+            for s in (0, 1):
+                k = spec.kind(h.index, a, s)
+                ok = k in (Boundary.MIRROR, Boundary.ANTIMIRROR) or (
+                    k == Boundary.FIXED and float(spec.value(h.index, a, s)) == 0.0
+                )
+                if not ok:
+                    raise ValueError(
+                        f"{who}: boundary {k.name} on face {_FACES[2 * a + s]} "
+                        f"of quantity {h.name or h.index}: the operator must be symmetric, "
+                        "linear and homogeneous (PERIODIC, FIXED(0), MIRROR or ANTIMIRROR); "
+                        "fold inhomogeneous boundary data into b"
+                    )
+
+
 class ConjugateGradient:
     def __init__(self, dd: DistributedDomain, operator: Stencil, x: DataHandle, b: DataHandle,
                  r: DataHandle, p: DataHandle, group_p: int = 0,
-                 group_x: Optional[int] = None):
+                 group_x: Optional[int] = None, preconditioner=None,
+                 z: Optional[DataHandle] = None):
         """dd is realized and holds x, b, r and p, four distinct quantities
         of one float type. group_p is the exchange group that moves p's
         halos (every iteration); group_x the one that moves x's (needed for
         solve(x0_zero=False) only). Raises ValueError for a non-symmetric
         stencil, a domain radius that does not cover it, mixed dtypes and a
         boundary kind on p or x other than PERIODIC, FIXED(0), MIRROR or
-        ANTIMIRROR."""
+        ANTIMIRROR.
+
+        preconditioner: None (plain CG), or any object with apply(r, z)
+        that leaves z = M r in curr[z] for a symmetric positive definite M
+        and reads r only (solvers/multigrid.py). It needs z, a fifth
+        distinct quantity of the same type."""
         if not dd._realized:
             raise ValueError("ConjugateGradient: construct after dd.realize()")
         hs = (x, b, r, p)
         if len({h.index for h in hs}) != 4:
             raise ValueError("ConjugateGradient: x, b, r and p must be four distinct quantities")
+        if preconditioner is not None:
+            if not callable(getattr(preconditioner, "apply", None)):
+                raise ValueError("ConjugateGradient: the preconditioner has no apply(r, z)")
+            if not isinstance(z, DataHandle) or z.index in {h.index for h in hs}:
+                raise ValueError(
+                    "ConjugateGradient: a preconditioner needs z, a fifth distinct quantity")
+            hs = hs + (z,)
+        elif z is not None:
+            raise ValueError("ConjugateGradient: z is given but no preconditioner")
         dt = x.dtype
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError(f"ConjugateGradient supports float32/float64 quantities, got {dt}")
         if any(h.dtype != dt for h in hs):
             raise ValueError(
-                "ConjugateGradient: x, b, r and p must share one dtype, got "
+                "ConjugateGradient: the quantities must share one dtype, got "
                 + ", ".join(str(h.dtype) for h in hs)
             )
-        if not operator.is_symmetric():
-            raise ValueError("ConjugateGradient: the stencil is not symmetric (w(o) != w(-o))")
-        need = operator.radius()
-        for dz in (-1, 0, 1):
-            for dy in (-1, 0, 1):
-                for dx in (-1, 0, 1):
-                    if (dx, dy, dz) != (0, 0, 0) and dd.radius.dir(dx, dy, dz) < need.dir(dx, dy, dz):
-                        raise ValueError(
-                            f"ConjugateGradient: the domain's radius {dd.radius.dir(dx, dy, dz)} in "
-                            f"direction {(dx, dy, dz)} does not cover the stencil's "
-                            f"{need.dir(dx, dy, dz)}"
-                        )
+        check_operator("ConjugateGradient", dd, operator)
         groups = dd.exchange_groups or [list(range(len(dd._data)))]
         if not (0 <= group_p < len(groups) and p.index in groups[group_p]):
             raise ValueError(f"ConjugateGradient: p is not in exchange group {group_p}")
         if group_x is not None and not (0 <= group_x < len(groups) and x.index in groups[group_x]):
             raise ValueError(f"ConjugateGradient: x is not in exchange group {group_x}")
-        spec = dd.boundary
-        if spec is not None:
-            for h in (p, x):
-                for a in range(3):
-                    if spec.periodic[a]:
-                        continue
-                    for s in (0, 1):
-                        k = spec.kind(h.index, a, s)
-                        ok = k in (Boundary.MIRROR, Boundary.ANTIMIRROR) or (
-                            k == Boundary.FIXED and float(spec.value(h.index, a, s)) == 0.0
-                        )
-                        if not ok:
-                            raise ValueError(
-                                f"ConjugateGradient: boundary {k.name} on face {_FACES[2 * a + s]} "
-                                f"of quantity {h.name or h.index}: the operator must be symmetric, "
-                                "linear and homogeneous (PERIODIC, FIXED(0), MIRROR or ANTIMIRROR); "
-                                "fold inhomogeneous boundary data into b"
-                            )
+        check_boundary("ConjugateGradient", dd, (p, x))
         self.dd, self.A = dd, operator
         self.x, self.b, self.r, self.p = x, b, r, p
         self.group_p, self.group_x = group_p, group_x
@@ -122,6 +159,9 @@ class ConjugateGradient:
         # host sync): operator = apply + exchange, dot = p . A p,
         # update = cg_update + the p update
         self.phase_times = {"operator": 0.0, "dot": 0.0, "update": 0.0}
+        self.M, self.z = preconditioner, z
+        if preconditioner is not None:
+            self.phase_times["precond"] = 0.0  # z = M r and r . z
 
     def _apply(self, h: DataHandle, group: int, overlap: bool):
         """next[h] = A curr[h] on every local domain, halos refreshed"""
@@ -168,6 +208,8 @@ class ConjugateGradient:
         limit = tol * tol * bb
         if rr <= limit:
             return CGResult(True, 0, residuals, "converged")
+        if self.M is not None:
+            return self._iterate_preconditioned(limit, bb, residuals, max_iter, overlap)
         for it in range(1, max_iter + 1):
             t0 = time.perf_counter()
             self._apply(p, self.group_p, overlap)
@@ -191,4 +233,51 @@ class ConjugateGradient:
             dd.backend.sync_compute()  # before the next exchange reads p
             rr = rr_new
             self.phase_times["update"] += time.perf_counter() - t2
+        return CGResult(False, max_iter, residuals, "max_iter")
+
+    def _precondition(self) -> float:
+        """z = M r; returns r . z"""
+        t0 = time.perf_counter()
+        self.M.apply(self.r, self.z)
+        rz = self.dd.dot(self.r, self.z)
+        self.phase_times["precond"] += time.perf_counter() - t0
+        return rz
+
+    def _iterate_preconditioned(self, limit, bb, residuals, max_iter, overlap) -> CGResult:
+        """the loop of solve() with z = M r in the place of r: p = z,
+        alpha = r.z / p.Ap, beta = r.z' / r.z. The stopping test and
+        `residuals` stay on r . r, which cg_update still returns. A
+        non-finite or non-positive r . z (M not positive definite) is a
+        breakdown."""
+        dd, x, r, p, z = self.dd, self.x, self.r, self.p, self.z
+        rz = self._precondition()
+        if not (math.isfinite(rz) and rz > 0.0):
+            return CGResult(False, 0, residuals, "breakdown")
+        dd.axpby(1.0, z, 0.0, z, out=p)
+        dd.backend.sync_compute()
+        for it in range(1, max_iter + 1):
+            t0 = time.perf_counter()
+            self._apply(p, self.group_p, overlap)
+            t1 = time.perf_counter()
+            pap = dd.dot(p, Next(p))
+            t2 = time.perf_counter()
+            self.phase_times["operator"] += t1 - t0
+            self.phase_times["dot"] += t2 - t1
+            if not (math.isfinite(pap) and pap > 0.0):
+                return CGResult(False, it - 1, residuals, "breakdown")
+            rr_new = dd.cg_update(rz / pap, x, p, r)
+            self.phase_times["update"] += time.perf_counter() - t2
+            if not math.isfinite(rr_new):
+                return CGResult(False, it, residuals + [float("nan")], "breakdown")
+            residuals.append(math.sqrt(rr_new / bb))
+            if rr_new <= limit:
+                return CGResult(True, it, residuals, "converged")
+            rz_new = self._precondition()
+            if not (math.isfinite(rz_new) and rz_new > 0.0):
+                return CGResult(False, it, residuals, "breakdown")
+            t3 = time.perf_counter()
+            dd.axpby(1.0, z, rz_new / rz, p, out=p)
+            dd.backend.sync_compute()  # before the next exchange reads p
+            rz = rz_new
+            self.phase_times["update"] += time.perf_counter() - t3
         return CGResult(False, max_iter, residuals, "max_iter")

@@ -390,6 +390,82 @@ class TorchBackend:
             be = torch.tensor(beta, dtype=tx.dtype, device=tx.device)
             tout.copy_(al * tx + be * ty)
 
+    def field_axpbypcz(self, boxes, alpha, x, x_next, beta, y, y_next, gamma, z, z_next, out,
+                       out_next, stream_id=0):
+        """out = alpha * x + beta * y + gamma * z in the quantity's type, the
+        coefficients rounded to it once; summed left to right, no FMA"""
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_axpbypcz", li, lo, hi,
+                                   [(x, x_next), (y, y_next), (z, z_next), (out, out_next)])
+            if v is None:
+                continue
+            tx, ty, tz, tout = v
+            al, be, ga = (torch.tensor(c, dtype=tx.dtype, device=tx.device)
+                          for c in (alpha, beta, gamma))
+            tout.copy_(al * tx + be * ty + ga * tz)
+
+    # ---- grid transfer: slicing references of csrc/src/grid_transfer.hip ----
+    def device_of(self, li):
+        return self.domains[li].device
+
+    def _transfer_views(self, op, fine, fli, fops, cli, cops, lo, hi):
+        """(fine views over [2 lo, 2 hi), coarse views over [lo, hi)), or
+        None for an empty box; the native ops' checks, as ValueErrors"""
+        if not 0 <= fli < len(fine.domains) or not 0 <= cli < len(self.domains):
+            raise ValueError(f"{op}: no such domain")
+        fd, cd = fine.domains[fli], self.domains[cli]
+        sizes = []
+        for dom, ops in ((fd, fops), (cd, cops)):
+            for qi, _nxt in ops:
+                if not 0 <= qi < len(dom.elem_sizes):
+                    raise ValueError(f"{op}: no such quantity")
+                sizes.append(dom.elem_sizes[qi])
+        if any(es not in (4, 8) for es in sizes):
+            raise ValueError(f"{op}: float32/float64 quantities only")
+        if len(set(sizes)) != 1:
+            raise ValueError(f"{op}: operands differ in element size")
+        if fd.device != cd.device:
+            raise ValueError(f"{op}: fine and coarse domains are on different devices")
+        flo, fhi = tuple(2 * c for c in lo), tuple(2 * c for c in hi)
+        fv = fine._vector_views(op, fli, flo, fhi, fops)
+        cv = self._vector_views(op, cli, lo, hi, cops)
+        if fv is None or cv is None:
+            return None
+        return fv, cv
+
+    def grid_restrict(self, fine, fli, alpha, a, a_next, beta, b, b_next, cli, out, out_next,
+                      lo, hi, stream_id=0):
+        """self is the coarse backend: out(c) = 0.125 * the sum over the 8
+        children of alpha a + beta b, in the quantity's type"""
+        v = self._transfer_views("grid_restrict", fine, fli, [(a, a_next), (b, b_next)], cli,
+                                 [(out, out_next)], lo, hi)
+        if v is None:
+            return
+        (ta, tb), (tout,) = v
+        al = torch.tensor(alpha, dtype=ta.dtype, device=ta.device)
+        be = torch.tensor(beta, dtype=ta.dtype, device=ta.device)
+        val = al * ta + be * tb
+        ez, ey, ex = tout.shape
+        s = val.reshape(ez, 2, ey, 2, ex, 2)
+        acc = torch.zeros_like(tout)
+        for dz in (0, 1):
+            for dy in (0, 1):
+                for dx in (0, 1):
+                    acc += s[:, dz, :, dy, :, dx]
+        tout.copy_(acc * 0.125)
+
+    def grid_prolong_add(self, coarse, cli, src, src_next, fli, dst, dst_next, lo, hi,
+                         stream_id=0):
+        """self is the fine backend: dst(p) += src(p >> 1) over [2 lo, 2 hi)"""
+        v = coarse._transfer_views("grid_prolong_add", self, fli, [(dst, dst_next)], cli,
+                                   [(src, src_next)], lo, hi)
+        if v is None:
+            return
+        (tdst,), (tsrc,) = v
+        ez, ey, ex = tsrc.shape
+        tdst += tsrc[:, None, :, None, :, None].expand(ez, 2, ey, 2, ex, 2).reshape(
+            2 * ez, 2 * ey, 2 * ex)
+
     def cg_update(self, boxes, alpha, x, p, r, stream_id=0):
         """the unfused composition: x = 1 x + alpha p; r = 1 r + (-alpha) A p
         (A p in next[p]); returns each domain's dot(r, r)"""
