@@ -18,6 +18,13 @@ written counting as one pass: dot 2, cg_update 6, the p update 3; and the
 cost of one empty host sync of the compute stream. With --precond mg also
 axpbypcz 4, grid_restrict 2 + 1/8 and grid_prolong_add 2 + 1/8 passes over
 the fine grid.
+
+--coefficient one|smooth|jump solves (sigma I - div(k grad)) x = b instead,
+with k = 1, a smooth field of contrast 55 or a jump 1 : --contrast (see
+coefficient_field); --precond jacobi is the diagonal preconditioner it makes
+possible. The record then holds coefficient (and contrast), and --kernels
+adds diffusion_apply (3 passes: u, k, out) and scaled_update (5 passes, in
+place). Without --coefficient the output is what it was.
 """
 import argparse
 import json
@@ -41,6 +48,20 @@ _BOUNDARIES = {
 }
 
 
+def coefficient_field(kind, size, contrast=16.0):
+    """the (z, y, x) fp64 k field: 'smooth' = exp(1.5 sin(2 pi x/nx)
+    cos(2 pi y/ny) + 0.5 sin(2 pi z/nz)) (contrast 55), 'jump' = contrast
+    where x >= nx/2 and y < ny/2, else 1"""
+    nx, ny, nz = size
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    if kind == "smooth":
+        return np.exp(1.5 * np.sin(2 * np.pi * x / nx) * np.cos(2 * np.pi * y / ny)
+                      + 0.5 * np.sin(2 * np.pi * z / nz))
+    if kind == "jump":
+        return np.where((x >= nx / 2) & (y < ny / 2), float(contrast), 1.0)
+    raise ValueError(kind)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256, help="edge of the global cube")
@@ -55,7 +76,10 @@ def main():
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--kernels", type=int, default=0, metavar="N",
                     help="also time N back-to-back launches of each vector kernel")
-    ap.add_argument("--precond", default="none", choices=["none", "mg"])
+    ap.add_argument("--precond", default="none", choices=["none", "mg", "jacobi"])
+    ap.add_argument("--coefficient", default="none", choices=["none", "one", "smooth", "jump"],
+                    help="variable-coefficient operator with this k field")
+    ap.add_argument("--contrast", type=float, default=16.0, help="the high value of 'jump'")
     ap.add_argument("--tol", type=float, default=0.0,
                     help="0: exactly --iters iterations; > 0: solve to this tolerance")
     args = ap.parse_args()
@@ -65,9 +89,12 @@ def main():
     size = (args.size,) * 3
     app = Poisson3D(size, order=args.order, dtype=dtype, sigma=args.sigma, backend=args.backend,
                     gpus=gpus, boundary=_BOUNDARIES[args.boundary],
-                    preconditioner="multigrid" if args.precond == "mg" else None)
+                    preconditioner={"none": None, "mg": "multigrid", "jacobi": "jacobi"}[args.precond],
+                    coefficient=args.coefficient != "none")
     app.realize()
     dd = app.dd
+    if args.coefficient in ("smooth", "jump"):
+        app.set_coefficient(coefficient_field(args.coefficient, size, args.contrast))
     rng = np.random.default_rng(0)
     for li in range(dd.num_local()):
         lo, hi = dd.local_rect(li)
@@ -109,6 +136,12 @@ def main():
         "precond": args.precond,
         "tol": args.tol,
     }
+    if args.coefficient != "none":
+        out["coefficient"] = args.coefficient
+        if args.coefficient == "jump":
+            out["contrast"] = args.contrast
+        if app.jacobi is not None:
+            out["precond_ms"] = ph["precond"] / n * 1e3
     if args.tol > 0:
         out["iterations"] = res.iterations
         out["converged"] = res.converged
@@ -144,6 +177,12 @@ def main():
         # the reductions wait for their value: a window of k synchronous calls
         report("dot", 2, window(lambda: dd.dot(p, sa.Next(p))))
         report("cg_update", 6, window(lambda: dd.cg_update(1e-30, x, p, r)))
+        if app.op is not None:
+            # 3 passes: read u, read k, write; 5 passes in place: x, d, y, z, out
+            report("diffusion_apply", 3, window(lambda: app.op.apply(p, where="all")))
+            report("scaled_update", 5,
+                   window(lambda: dd.scaled_update(1.0, x, app.dinv, 1e-30, r, -1e-30, sa.Next(p),
+                                                   out=x)))
         if app.mg is not None:
             z, top = app.z, app.mg._levels[0]
             coarse = app.mg._levels[1]

@@ -115,6 +115,37 @@ enum class StencilType { F32, F64 };
 void stencil_apply(ExchangeEngine &eng, int dom, int64_t srcQ, int64_t dstQ, const Rect3 &region,
                    const StencilTaps &taps, StencilType type, int streamId = 0);
 
+// Variable-coefficient diffusion operator (csrc/src/diffusion_op.hip):
+//   next[dstQ](p) = sigma u(p) + sum over a in {x,y,z}, s in {-1,+1} of
+//                   h[a] * 0.5 (k(p) + k(p + s e_a)) * (u(p) - u(p + s e_a))
+// with u = curr[srcQ], k = curr[kQ] (a cell-centred coefficient of the same
+// type and layout) and h[a] = 1 / spacing_a^2, for every p in `region`
+// (global coords), on compute_stream(dom, streamId). The face coefficient
+// is the arithmetic mean of the two cells, so the operator is symmetric.
+// Arithmetic is in the quantity's own type; h and sigma are rounded to it
+// once, at launch; association and FMA contraction are unspecified.
+// stencil_apply's contract: nothing outside `region` is written in any
+// buffer, and only the cells of `region` and their six face neighbours, in
+// u and in k, enter the arithmetic (no edge or corner cell; the rest of a
+// 16 B line that holds a needed cell may be loaded but is never used).
+// Regions at least 8 cells wide whose curr[srcQ], curr[kQ] and next[dstQ]
+// rows are equally aligned modulo 16 B run the strip kernel, the rest a
+// linearised cell kernel. Throws std::invalid_argument, and launches
+// nothing, for an unknown domain or quantity, element sizes that do not
+// match `type` (4 / 8) or differ, a region outside full_region() or whose
+// 1-cell face apron leaves it, a streamId out of range and layouts that
+// differ. An empty region is a no-op.
+void diffusion_apply(ExchangeEngine &eng, int dom, int64_t srcQ, int64_t kQ, int64_t dstQ,
+                     const Rect3 &region, const double h[3], double sigma, StencilType type,
+                     int streamId = 0);
+// out(p) = omega / diag(p),  diag(p) = sigma + sum over a, s of
+// h[a] * 0.5 (k(p) + k(p + s e_a)), in the quantity's type; out is
+// (outQ, outNext). The containment contract and validation of
+// diffusion_apply. Runs once per coefficient change: one linearised kernel.
+void diffusion_inv_diagonal(ExchangeEngine &eng, int dom, int64_t kQ, int64_t outQ, bool outNext,
+                            const Rect3 &region, const double h[3], double sigma, double omega,
+                            int streamId = 0);
+
 // Vector operations on pitched quantities (csrc/src/vector_ops.hip): the
 // building blocks of Krylov solvers. Every op works on a global-coordinate
 // `region` of one local domain, on float32 or float64 quantities (all
@@ -153,6 +184,15 @@ void field_axpby(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNe
 void field_axpbypcz(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
                     double beta, int64_t y, bool yNext, double gamma, int64_t z, bool zNext,
                     int64_t out, bool outNext, const Rect3 &region, int streamId = 0);
+// out = alpha * x + d * (beta * y + gamma * z) with d a quantity (5 passes):
+// the diagonally scaled relaxation update e += (omega / diag) (f - A e) of
+// the variable-coefficient smoother. With aliased operands also the first
+// sweep e = d f (alpha = 0, gamma = 0) and the Jacobi preconditioner
+// z = d r. out may be the buffer of any input.
+void field_scaled_update(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                         int64_t d, bool dNext, double beta, int64_t y, bool yNext, double gamma,
+                         int64_t z, bool zNext, int64_t out, bool outNext, const Rect3 &region,
+                         int streamId = 0);
 // fused conjugate-gradient update, one pass instead of three:
 //   curr[x] += alpha * curr[p];  curr[r] -= alpha * next[p]
 // returning sum r_new^2 (fp64 accumulation of the rounded r_new). next[p]

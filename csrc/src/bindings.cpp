@@ -404,6 +404,49 @@ PYBIND11_MODULE(_C, m) {
       py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("gamma"), py::arg("z"),
       py::arg("z_next"), py::arg("out"), py::arg("out_next"), py::arg("region"),
       py::arg("stream_id") = 0);
+  m.def(
+      "field_scaled_update",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, int64_t d,
+                     bool dNext, double beta, int64_t y, bool yNext, double gamma, int64_t z,
+                     bool zNext, int64_t out, bool outNext, const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_scaled_update(eng, dom, alpha, x, xNext, d, dNext, beta, y, yNext, gamma, z,
+                              zNext, out, outNext, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
+      py::arg("d"), py::arg("d_next"), py::arg("beta"), py::arg("y"), py::arg("y_next"),
+      py::arg("gamma"), py::arg("z"), py::arg("z_next"), py::arg("out"), py::arg("out_next"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  // variable-coefficient diffusion operator (csrc/src/diffusion_op.hip)
+  m.def(
+      "diffusion_apply",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t srcQ, int64_t kQ, int64_t dstQ,
+                     const Rect3 &region, const std::array<double, 3> &h, double sigma,
+                     StencilType type, int streamId) {
+        value_errors([&] {
+          diffusion_apply(eng, dom, srcQ, kQ, dstQ, region, h.data(), sigma, type, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("src_q"), py::arg("k_q"), py::arg("dst_q"),
+      py::arg("region"), py::arg("h"), py::arg("sigma"), py::arg("type"),
+      py::arg("stream_id") = 0);
+  m.def(
+      "diffusion_inv_diagonal",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t kQ, int64_t outQ, bool outNext,
+                     const Rect3 &region, const std::array<double, 3> &h, double sigma,
+                     double omega, int streamId) {
+        value_errors([&] {
+          diffusion_inv_diagonal(eng, dom, kQ, outQ, outNext, region, h.data(), sigma, omega,
+                                 streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("k_q"), py::arg("out_q"), py::arg("out_next"),
+      py::arg("region"), py::arg("h"), py::arg("sigma"), py::arg("omega"),
+      py::arg("stream_id") = 0);
   // grid transfer (csrc/src/grid_transfer.hip)
   m.def(
       "grid_restrict",

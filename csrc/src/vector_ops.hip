@@ -1,5 +1,6 @@
 // Vector operations on pitched quantities for gfx950: the inner product,
-// out = alpha x + beta y, out = alpha x + beta y + gamma z, and the fused
+// out = alpha x + beta y, out = alpha x + beta y + gamma z, the diagonally
+// scaled out = alpha x + d (beta y + gamma z), and the fused
 // conjugate-gradient update. Pure
 // streaming kernels: every cell of the region is read (and written) once.
 //
@@ -172,6 +173,17 @@ template <typename T> struct AxpbypczF {
   }
 };
 
+template <typename T> struct ScaledF {
+  const char *x, *d, *y, *z;
+  char *out;
+  T alpha, beta, gamma;
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vx = *(const V *)(x + off), vd = *(const V *)(d + off);
+    const V vy = *(const V *)(y + off), vz = *(const V *)(z + off);
+    *(V *)(out + off) = alpha * vx + vd * (beta * vy + gamma * vz);
+  }
+};
+
 template <typename T> struct CgF {
   char *x, *r;
   const char *p, *ap;
@@ -207,6 +219,14 @@ __global__ void __launch_bounds__(256)
     axpbypcz_kernel(Geom g, const char *x, const char *y, const char *z, char *out, T alpha,
                     T beta, T gamma) {
   AxpbypczF<T> f{x, y, z, out, alpha, beta, gamma};
+  walk<T, STRIPS>(g, f);
+}
+
+template <typename T, bool STRIPS>
+__global__ void __launch_bounds__(256)
+    scaled_update_kernel(Geom g, const char *x, const char *d, const char *y, const char *z,
+                         char *out, T alpha, T beta, T gamma) {
+  ScaledF<T> f{x, d, y, z, out, alpha, beta, gamma};
   walk<T, STRIPS>(g, f);
 }
 
@@ -449,6 +469,28 @@ void field_axpbypcz(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool 
   } else {
     VEC_OPS_LAUNCH(double, l, axpbypcz_kernel, stream, l.g, (const char *)l.ptr[0],
                    (const char *)l.ptr[1], (const char *)l.ptr[2], l.ptr[3], alpha, beta, gamma);
+  }
+}
+
+void field_scaled_update(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                         int64_t d, bool dNext, double beta, int64_t y, bool yNext, double gamma,
+                         int64_t z, bool zNext, int64_t out, bool outNext, const Rect3 &region,
+                         int streamId) {
+  const Launch l =
+      plan_launch("field_scaled_update", eng, dom,
+                  {{x, xNext}, {d, dNext}, {y, yNext}, {z, zNext}, {out, outNext}}, region);
+  if (l.empty) return;
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  if (l.es == 4) {
+    const float al = (float)alpha, be = (float)beta, ga = (float)gamma; // rounded once
+    VEC_OPS_LAUNCH(float, l, scaled_update_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], (const char *)l.ptr[2], (const char *)l.ptr[3],
+                   l.ptr[4], al, be, ga);
+  } else {
+    VEC_OPS_LAUNCH(double, l, scaled_update_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], (const char *)l.ptr[2], (const char *)l.ptr[3],
+                   l.ptr[4], alpha, beta, gamma);
   }
 }
 

@@ -373,9 +373,16 @@ class DistributedDomain:
         taps that reach outside the allocated halo)."""
         dst = src if dst is None else dst
         dt = self._stencil_dtype(src, dst)
+        boxes, sid = self._operator_boxes("apply_stencil", where, stream_id)
+        for li, bs in enumerate(boxes):
+            for lo, hi in bs:
+                self.backend.stencil_apply(li, src.index, dst.index, lo, hi, stencil, dt, sid)
+
+    def _operator_boxes(self, op: str, where, stream_id: Optional[int]):
+        """(per local domain: the boxes of `where`, the compute stream id)"""
         if isinstance(where, str):
             if where not in ("all", "interior", "exterior"):
-                raise ValueError(f"apply_stencil: where={where!r}")
+                raise ValueError(f"{op}: where={where!r}")
             if where == "all":
                 boxes = [[self.local_rect(li)] for li in range(self.num_local())]
             elif where == "interior":
@@ -387,9 +394,35 @@ class DistributedDomain:
             lo, hi = where
             boxes = [[(tuple(lo), tuple(hi))] for _ in range(self.num_local())]
             sid = 0 if stream_id is None else stream_id
+        return boxes, sid
+
+    def apply_diffusion(self, k: DataHandle, src: DataHandle, dst: Optional[DataHandle] = None,
+                        spacing=(1.0, 1.0, 1.0), sigma: float = 0.0, where="all",
+                        stream_id: Optional[int] = None):
+        """next[dst] = (sigma I - div(k grad)) curr[src] on every local
+        domain (dst=None: the same quantity), k a cell-centred coefficient
+        quantity of the same type:
+
+            (A u)(p) = sigma u(p) + sum over a in {x,y,z}, s in {-1,+1} of
+                       h_a * 0.5 (k(p) + k(p + s e_a)) * (u(p) - u(p + s e_a))
+
+        with h_a = 1 / spacing_a^2. `where` and `stream_id` are those of
+        apply_stencil. The face halos of src AND of k must be current
+        (exchange() of their groups) except for where="interior"; edge and
+        corner halos are never read. float32/float64 quantities only
+        (ValueError otherwise, also for a box whose 1-cell face apron
+        leaves the allocation). solvers/diffusion.py wraps this as an
+        operator for ConjugateGradient and GeometricMultigrid."""
+        dst = src if dst is None else dst
+        dt = self._stencil_dtype(src, dst)
+        if k.dtype != dt:
+            raise ValueError(f"apply_diffusion: k is {k.dtype} but src is {dt}")
+        h = [1.0 / (float(s) * float(s)) for s in spacing]
+        boxes, sid = self._operator_boxes("apply_diffusion", where, stream_id)
         for li, bs in enumerate(boxes):
             for lo, hi in bs:
-                self.backend.stencil_apply(li, src.index, dst.index, lo, hi, stencil, dt, sid)
+                self.backend.diffusion_apply(li, src.index, k.index, dst.index, lo, hi, h,
+                                             float(sigma), dt, sid)
 
     def step_stencil(self, stencil, src: DataHandle, dst: Optional[DataHandle] = None,
                      overlap: bool = True):
@@ -481,6 +514,20 @@ class DistributedDomain:
         boxes = self._vector_boxes("axpbypcz", where)
         self.backend.field_axpbypcz(boxes, float(alpha), qx, nx, float(beta), qy, ny,
                                     float(gamma), qz, nz, qo, no)
+
+    def scaled_update(self, alpha: float, x, d, beta: float, y, gamma: float, z, out,
+                      where="all"):
+        """out = alpha * x + d * (beta * y + gamma * z), element-wise, with
+        d a quantity (one 5-pass kernel): the diagonally scaled relaxation
+        update e += (omega / diag) (f - A e) of the variable-coefficient
+        smoother; with aliased operands also e = d f and the Jacobi
+        preconditioner z = d r. out may be the buffer of any input.
+        Enqueued on compute stream 0 like axpby."""
+        (qx, nx), (qd, nd), (qy, ny), (qz, nz), (qo, no) = self._vector_operands(
+            "scaled_update", [x, d, y, z, out])
+        boxes = self._vector_boxes("scaled_update", where)
+        self.backend.field_scaled_update(boxes, float(alpha), qx, nx, qd, nd, float(beta), qy, ny,
+                                         float(gamma), qz, nz, qo, no)
 
     def cg_update(self, alpha: float, x, p, r) -> float:
         """the fused conjugate-gradient update over every local_rect:

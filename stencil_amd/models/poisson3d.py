@@ -23,6 +23,7 @@ from ..boundary import FACES, Boundary, parse_face
 from ..core import DistributedDomain
 from ..parallel.placement import PlacementStrategy
 from ..solvers.cg import CGResult, ConjugateGradient
+from ..solvers.diffusion import DiffusionOperator, JacobiPreconditioner
 from ..solvers.multigrid import GeometricMultigrid
 from ..stencil import Stencil
 
@@ -43,6 +44,7 @@ class Poisson3D:
         preconditioner: Optional[str] = None,
         mg: Optional[dict] = None,
         coarse_order: int = 2,
+        coefficient: bool = False,
     ):
         """A = sigma I - laplacian(order, spacing); sigma >= 0.
 
@@ -50,6 +52,18 @@ class Poisson3D:
         level l >= 1 uses sigma I - laplacian(coarse_order, spacing * 2^l).
         mg: keyword arguments of GeometricMultigrid (nu, omega,
         coarse_sweeps, max_levels).
+
+        coefficient=True: A = sigma I - div(k grad) with a cell-centred
+        coefficient field k (solvers/diffusion.py), initially 1; give it
+        with set_coefficient(). Needs order == 2 (ValueError otherwise).
+        Three more quantities: k in an exchange group of its own (CLAMP on
+        non-periodic faces), dinv, and xc, with which the solver verifies
+        the true residual b - A x at convergence and refines x until it
+        meets the tolerance (ConjugateGradient.solve; a variable k makes
+        nearly singular operators common, where the recursive residual of
+        a float32 solve drifts). The multigrid hierarchy is then built
+        from k, and preconditioner may also be "jacobi" (diagonal scaling;
+        ValueError without a coefficient).
 
         boundary: {face: kind | (kind, value)} as in Diffusion3D, applied
         to all four quantities; None = fully periodic. The kinds the
@@ -60,11 +74,18 @@ class Poisson3D:
         sigma = float(sigma)
         if not sigma >= 0.0:
             raise ValueError(f"Poisson3D: sigma must be >= 0, got {sigma}")
-        if preconditioner not in (None, "multigrid"):
+        if preconditioner not in (None, "multigrid", "jacobi"):
             raise ValueError(
-                f"Poisson3D: preconditioner is None or 'multigrid', got {preconditioner!r}")
-        if mg is not None and preconditioner is None:
-            raise ValueError("Poisson3D: mg is given but no preconditioner")
+                "Poisson3D: preconditioner is None, 'multigrid' or 'jacobi', "
+                f"got {preconditioner!r}")
+        if preconditioner == "jacobi" and not coefficient:
+            raise ValueError("Poisson3D: the 'jacobi' preconditioner needs coefficient=True "
+                             "(the constant-coefficient diagonal is a multiple of I)")
+        if coefficient and order != 2:
+            raise ValueError(f"Poisson3D: coefficient=True needs order == 2, got {order}")
+        if mg is not None and preconditioner != "multigrid":
+            raise ValueError("Poisson3D: mg is given but no multigrid preconditioner")
+        self.coefficient = bool(coefficient)
         self.sigma = sigma
         self.order, self.coarse_order = order, coarse_order
         self.spacing = tuple(float(h) for h in spacing)
@@ -106,11 +127,22 @@ class Poisson3D:
         if preconditioner is not None:
             self.z = self.dd.add_data(dt, "z")
             groups.append([self.z.index])
+        self.k = self.dinv = self.xc = None
+        self.op: Optional[DiffusionOperator] = None
+        self.jacobi: Optional[JacobiPreconditioner] = None
+        if self.coefficient:
+            self.k = self.dd.add_data(dt, "k")
+            self.dinv = self.dd.add_data(dt, "dinv")
+            self.xc = self.dd.add_data(dt, "xc")  # CG's correction: true-residual check
+            self._group_k = len(groups)
+            groups.append([self.k.index])
         self.dd.set_exchange_groups(groups)
         if boundary:
             for face, spec in boundary.items():
                 kind, value = spec if isinstance(spec, (tuple, list)) else (spec, 0)
                 self.dd.set_boundary(face, kind, value)
+                if self.coefficient and Boundary(kind) != Boundary.PERIODIC:
+                    self.dd.set_boundary(face, Boundary.CLAMP, quantities=[self.k])
         self.cg: Optional[ConjugateGradient] = None
 
     def operator_at(self, level: int) -> Stencil:
@@ -125,10 +157,42 @@ class Poisson3D:
 
     def realize(self):
         self.dd.realize()
-        if self.preconditioner is not None:
-            self.mg = GeometricMultigrid(self.dd, self.operator_at, self.z, 2, **self._mg_args)
-        self.cg = ConjugateGradient(self.dd, self.stencil, self.x, self.b, self.r, self.p,
-                                    group_p=0, group_x=1, preconditioner=self.mg, z=self.z)
+        operator, operator_at = self.stencil, self.operator_at
+        if self.coefficient:
+            ones = np.ones((self.dd.size[2], self.dd.size[1], self.dd.size[0]), dtype=self.k.dtype)
+            self._scatter(self.k, ones)
+            self.op = DiffusionOperator(self.dd, self.k, self._group_k, spacing=self.spacing,
+                                        sigma=self.sigma, dinv=self.dinv)
+            self.op.refresh()
+            operator, operator_at = self.op, (lambda level: self.op)
+        M = None
+        if self.preconditioner == "multigrid":
+            M = self.mg = GeometricMultigrid(self.dd, operator_at, self.z, 2, **self._mg_args)
+        elif self.preconditioner == "jacobi":
+            M = self.jacobi = JacobiPreconditioner(self.op)
+        self.cg = ConjugateGradient(self.dd, operator, self.x, self.b, self.r, self.p,
+                                    group_p=0, group_x=1, preconditioner=M, z=self.z,
+                                    correction=self.xc)
+
+    def set_coefficient(self, global_array):
+        """k = the (z, y, x) global array, every value finite and > 0
+        (ValueError otherwise; nothing is written then); refreshes the
+        operator's halos, the preconditioner's diagonal and the multigrid
+        hierarchy. Realizes the domain first if need be."""
+        if not self.coefficient:
+            raise ValueError("Poisson3D.set_coefficient: built with coefficient=False")
+        g = np.asarray(global_array)
+        if not (np.isfinite(g).all() and (g > 0).all()):
+            raise ValueError("Poisson3D.set_coefficient: every value must be finite and > 0")
+        if self.cg is None:
+            self.realize()
+        self._scatter(self.k, g)
+        if self.mg is not None:
+            self.mg.refresh_coefficients()
+        else:
+            self.op.refresh()
+        if self.jacobi is not None:
+            self.jacobi.refresh()
 
     def _scatter(self, handle, g):
         g = np.asarray(g)

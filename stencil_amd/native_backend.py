@@ -740,6 +740,43 @@ class NativeBackend:
             _C.field_axpbypcz(self.engine, li, alpha, x, x_next, beta, y, y_next, gamma, z, z_next,
                               out, out_next, _rect3(lo, hi), stream_id)
 
+    def field_scaled_update(self, boxes, alpha: float, x: int, x_next: bool, d: int, d_next: bool,
+                            beta: float, y: int, y_next: bool, gamma: float, z: int,
+                            z_next: bool, out: int, out_next: bool, stream_id: int = 0):
+        """out = alpha * x + d * (beta * y + gamma * z) over each local
+        domain's box, d a quantity; out may alias any input. Enqueued, not
+        awaited."""
+        for li, (lo, hi) in enumerate(boxes):
+            _C.field_scaled_update(self.engine, li, alpha, x, x_next, d, d_next, beta, y, y_next,
+                                   gamma, z, z_next, out, out_next, _rect3(lo, hi), stream_id)
+
+    # ---- variable-coefficient diffusion (csrc/src/diffusion_op.hip) ----
+    @staticmethod
+    def _stencil_type(op: str, dtype):
+        import numpy as np
+
+        dt = np.dtype(dtype)
+        if dt == np.float32:
+            return _C.StencilType.F32
+        if dt == np.float64:
+            return _C.StencilType.F64
+        raise ValueError(f"{op} supports float32/float64, got {dt}")
+
+    def diffusion_apply(self, li: int, src_qi: int, k_qi: int, dst_qi: int, lo: Vec, hi: Vec,
+                        h, sigma: float, dtype, stream_id: int = 0):
+        """next[dst_qi] = (sigma I - div(k grad)) curr[src_qi] over the
+        global box [lo, hi), k = curr[k_qi], h[a] = 1 / spacing_a^2. Raises
+        ValueError, launching nothing, as diffusion_apply in ops.hpp."""
+        _C.diffusion_apply(self.engine, li, src_qi, k_qi, dst_qi, _rect3(lo, hi),
+                           [float(v) for v in h], float(sigma),
+                           self._stencil_type("diffusion_apply", dtype), stream_id)
+
+    def diffusion_inv_diagonal(self, li: int, k_qi: int, out_qi: int, out_next: bool, lo: Vec,
+                               hi: Vec, h, sigma: float, omega: float, stream_id: int = 0):
+        """out = omega / diag of the diffusion operator over the global box"""
+        _C.diffusion_inv_diagonal(self.engine, li, k_qi, out_qi, out_next, _rect3(lo, hi),
+                                  [float(v) for v in h], float(sigma), float(omega), stream_id)
+
     # ---- grid transfer (csrc/src/grid_transfer.hip) ----
     # self is the DESTINATION backend: its compute stream carries the kernel.
     # Boxes are coarse global boxes; the caller has synced the source side.

@@ -14,7 +14,11 @@ stream of the given ExchangeEngine; regions are global-coordinate Rect3s.
   out = alpha x + beta y and the fused conjugate-gradient update on pitched
   quantities (csrc/src/vector_ops.hip); field_dot_begin / cg_update_begin
   + reduction_end split a reduction so that several local domains launch
-  before any of them waits
+  before any of them waits; field_scaled_update: out = alpha x + d (beta y +
+  gamma z) with d a quantity
+- diffusion_apply / diffusion_inv_diagonal: the variable-coefficient
+  operator sigma I - div(k grad) and omega over its diagonal
+  (csrc/src/diffusion_op.hip)
 """
 from .._C import (  # noqa: F401
     FieldStats,
@@ -23,9 +27,12 @@ from .._C import (  # noqa: F401
     StencilType,
     cg_update,
     cg_update_begin,
+    diffusion_apply,
+    diffusion_inv_diagonal,
     field_axpby,
     field_dot,
     field_dot_begin,
+    field_scaled_update,
     field_stats,
     fill_f32,
     init_harmonic_f64,
@@ -43,9 +50,12 @@ __all__ = [
     "StencilType",
     "cg_update",
     "cg_update_begin",
+    "diffusion_apply",
+    "diffusion_inv_diagonal",
     "field_axpby",
     "field_dot",
     "field_dot_begin",
+    "field_scaled_update",
     "field_stats",
     "fill_f32",
     "init_harmonic_f64",

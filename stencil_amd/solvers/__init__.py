@@ -1,8 +1,11 @@
 """Linear solvers on top of the stencil operator and the vector operations
-of DistributedDomain (dot, axpby, axpbypcz, cg_update), and the geometric
-multigrid preconditioner with its grid transfer."""
+of DistributedDomain (dot, axpby, axpbypcz, scaled_update, cg_update), the
+variable-coefficient diffusion operator with its Jacobi preconditioner, and
+the geometric multigrid preconditioner with its grid transfer."""
 from .cg import CGResult, ConjugateGradient
+from .diffusion import DiffusionOperator, JacobiPreconditioner
 from .multigrid import GeometricMultigrid
 from .transfer import GridTransfer
 
-__all__ = ["CGResult", "ConjugateGradient", "GeometricMultigrid", "GridTransfer"]
+__all__ = ["CGResult", "ConjugateGradient", "DiffusionOperator", "GeometricMultigrid",
+           "GridTransfer", "JacobiPreconditioner"]

@@ -1,7 +1,9 @@
 """Conjugate gradients for A x = b with A a symmetric positive definite
 stencil operator.
 
-The operator is a `Stencil` applied by `DistributedDomain.apply_stencil`;
+The operator is a `Stencil` applied by `DistributedDomain.apply_stencil`, or
+a `DiffusionOperator` (solvers/diffusion.py: sigma I - div(k grad) with a
+coefficient field k, whose halos the caller keeps current with refresh());
 the halo exchange and the boundary fill of the quantity `p` supply the
 neighbour values, so the domain's boundary kinds ARE the discrete boundary
 conditions of A. The solver never calls `dd.swap()`: `A p` lives in the
@@ -25,6 +27,20 @@ symmetric positive definite; solvers/multigrid.py) and a fifth quantity z:
              z = M r; rz_new = dot(r, z);  p = z + (rz_new / rz) * p
 
 Without one the code path is the loop above, unchanged.
+
+With a `correction` quantity d the solver also verifies what it returns.
+The recursive r drifts from b - A x by the roundings of x += alpha p; when
+||x|| is large against ||b|| (a nearly singular A: a small sigma on a
+periodic or MIRROR box) a float32 solve "converges" with a true residual
+several times the tolerance. So after convergence:
+
+    repeat:  exchange(group_x); r = b - A x;  done if ||r|| <= tol ||b||
+             d = 0; CG (as above) on A d = r to the same absolute threshold
+             x = x + d
+
+which rounds x once per correction instead of once per iteration
+(iterative refinement in the working precision; a correction solve takes a
+handful of iterations). Without `correction` nothing of this runs.
 
 Boundary conditions. CG needs A symmetric, and linear and homogeneous in
 the field: PERIODIC, FIXED(0), MIRROR and ANTIMIRROR qualify (for star
@@ -60,14 +76,23 @@ class CGResult:
     # relative recursive residual norm sqrt(r.r / b.b) after each iteration;
     # entry 0 is the initial one (1.0 when x0 = 0)
     residuals: List[float] = field(default_factory=list)
-    reason: str = ""  # "converged" | "max_iter" | "breakdown" | "zero_rhs"
+    # "converged" | "max_iter" | "breakdown" | "zero_rhs" | "stagnated"
+    reason: str = ""
 
 
 _FACES = ("x-", "x+", "y-", "y+", "z-", "z+")
 
 
-def check_operator(who: str, dd: DistributedDomain, operator: Stencil):
-    """ValueError unless the stencil is symmetric and dd's radius covers it"""
+def check_operator(who: str, dd: DistributedDomain, operator):
+    """ValueError unless the operator (a Stencil or a DiffusionOperator) is
+    symmetric and dd's radius covers it"""
+    if not isinstance(operator, Stencil):
+        from .diffusion import DiffusionOperator
+
+        if not isinstance(operator, DiffusionOperator):
+            raise ValueError(f"{who}: the operator is a Stencil or a DiffusionOperator")
+        if operator.dd is not dd:
+            raise ValueError(f"{who}: the DiffusionOperator belongs to another domain")
     if not operator.is_symmetric():
         raise ValueError(f"{who}: the stencil is not symmetric (w(o) != w(-o))")
     need = operator.radius()
@@ -107,13 +132,14 @@ def check_boundary(who: str, dd: DistributedDomain, handles):
 
 
 class ConjugateGradient:
-    def __init__(self, dd: DistributedDomain, operator: Stencil, x: DataHandle, b: DataHandle,
+    def __init__(self, dd: DistributedDomain, operator, x: DataHandle, b: DataHandle,
                  r: DataHandle, p: DataHandle, group_p: int = 0,
                  group_x: Optional[int] = None, preconditioner=None,
-                 z: Optional[DataHandle] = None):
+                 z: Optional[DataHandle] = None, correction: Optional[DataHandle] = None):
         """dd is realized and holds x, b, r and p, four distinct quantities
-        of one float type. group_p is the exchange group that moves p's
-        halos (every iteration); group_x the one that moves x's (needed for
+        of one float type. operator is a Stencil or a DiffusionOperator of
+        dd (of the same float type). group_p is the exchange group that
+        moves p's halos (every iteration); group_x the one that moves x's (needed for
         solve(x0_zero=False) only). Raises ValueError for a non-symmetric
         stencil, a domain radius that does not cover it, mixed dtypes and a
         boundary kind on p or x other than PERIODIC, FIXED(0), MIRROR or
@@ -122,7 +148,12 @@ class ConjugateGradient:
         preconditioner: None (plain CG), or any object with apply(r, z)
         that leaves z = M r in curr[z] for a symmetric positive definite M
         and reads r only (solvers/multigrid.py). It needs z, a fifth
-        distinct quantity of the same type."""
+        distinct quantity of the same type.
+
+        correction: None, or one more distinct quantity of the same type.
+        solve() then verifies the TRUE residual b - A x once the recursive
+        one has converged, and refines until it meets the tolerance too
+        (see solve()). Needs group_x."""
         if not dd._realized:
             raise ValueError("ConjugateGradient: construct after dd.realize()")
         hs = (x, b, r, p)
@@ -137,6 +168,13 @@ class ConjugateGradient:
             hs = hs + (z,)
         elif z is not None:
             raise ValueError("ConjugateGradient: z is given but no preconditioner")
+        if correction is not None:
+            if not isinstance(correction, DataHandle) or correction.index in {h.index for h in hs}:
+                raise ValueError("ConjugateGradient: correction must be one more distinct quantity")
+            if group_x is None:
+                raise ValueError("ConjugateGradient: correction needs group_x, the exchange "
+                                 "group of x")
+            hs = hs + (correction,)
         dt = x.dtype
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError(f"ConjugateGradient supports float32/float64 quantities, got {dt}")
@@ -146,6 +184,9 @@ class ConjugateGradient:
                 + ", ".join(str(h.dtype) for h in hs)
             )
         check_operator("ConjugateGradient", dd, operator)
+        if not isinstance(operator, Stencil) and operator.k.dtype != dt:
+            raise ValueError(
+                f"ConjugateGradient: the coefficient is {operator.k.dtype}, the unknown {dt}")
         groups = dd.exchange_groups or [list(range(len(dd._data)))]
         if not (0 <= group_p < len(groups) and p.index in groups[group_p]):
             raise ValueError(f"ConjugateGradient: p is not in exchange group {group_p}")
@@ -159,20 +200,26 @@ class ConjugateGradient:
         # host sync): operator = apply + exchange, dot = p . A p,
         # update = cg_update + the p update
         self.phase_times = {"operator": 0.0, "dot": 0.0, "update": 0.0}
-        self.M, self.z = preconditioner, z
+        self.M, self.z, self.correction = preconditioner, z, correction
         if preconditioner is not None:
             self.phase_times["precond"] = 0.0  # z = M r and r . z
 
     def _apply(self, h: DataHandle, group: int, overlap: bool):
         """next[h] = A curr[h] on every local domain, halos refreshed"""
         dd = self.dd
+        if isinstance(self.A, Stencil):
+            def op(where):
+                dd.apply_stencil(self.A, h, where=where)
+        else:  # a DiffusionOperator
+            def op(where):
+                self.A.apply(h, where=where)
         if overlap:
-            dd.apply_stencil(self.A, h, where="interior")
+            op("interior")
             dd.exchange(group)
-            dd.apply_stencil(self.A, h, where="exterior")
+            op("exterior")
         else:
             dd.exchange(group)
-            dd.apply_stencil(self.A, h, where="all")
+            op("all")
         dd.backend.sync_compute()
 
     def solve(self, tol: float = 1e-6, max_iter: int = 1000, x0_zero: bool = True,
@@ -181,7 +228,64 @@ class ConjugateGradient:
         max_iter. x0_zero=True starts from x = 0 (x's content is
         overwritten); False starts from curr[x] and needs group_x.
         b = 0 gives x = 0 in 0 iterations. A non-positive or non-finite
-        p . A p ends the solve with converged=False, reason="breakdown"."""
+        p . A p ends the solve with converged=False, reason="breakdown".
+
+        With a `correction` quantity d the recursive residual is not
+        trusted: in the quantity's type it drifts from b - A x by the
+        roundings of x += alpha p, visibly so when ||x|| is large against
+        ||b|| (a nearly singular A in float32). Once it has converged,
+        r = b - A x is computed; if ||r|| <= tol ||b|| the solve is done
+        (the last entry of `residuals` is then this true residual).
+        Otherwise A d = r is solved from d = 0 to the same absolute
+        threshold, x += d (one rounding of x instead of one per iteration)
+        and the check is repeated. The iterations of the correction solves
+        count and are limited by max_iter like the others. A true residual
+        that a correction does not bring below 0.9 x the previous one ends
+        the solve with converged=False, reason="stagnated": the tolerance
+        is then below what the type can resolve."""
+        res = self._solve(tol, max_iter, x0_zero, overlap)
+        if self.correction is None or not res.converged or res.reason == "zero_rhs":
+            return res
+        return self._refine(res, tol, max_iter, overlap)
+
+    def _refine(self, res: CGResult, tol, max_iter, overlap) -> CGResult:
+        dd, x, b, r, p, d = self.dd, self.x, self.b, self.r, self.p, self.correction
+        bb = dd.dot(b)
+        limit = tol * tol * bb
+        residuals, its, prev = list(res.residuals), res.iterations, None
+        while True:
+            self._apply(x, self.group_x, overlap)
+            dd.axpby(1.0, b, -1.0, Next(x), out=r)
+            rr = dd.dot(r)
+            if not math.isfinite(rr):
+                return CGResult(False, its, residuals[:-1] + [float("nan")], "breakdown")
+            residuals[-1] = math.sqrt(rr / bb)
+            if rr <= limit:
+                return CGResult(True, its, residuals, "converged")
+            if prev is not None and rr > 0.81 * prev:  # squares: 0.9 in norm
+                return CGResult(False, its, residuals, "stagnated")
+            if its >= max_iter:
+                return CGResult(False, its, residuals, "max_iter")
+            prev = rr
+            dd.axpby(0.0, r, 0.0, r, out=d)
+            dd.axpby(1.0, r, 0.0, r, out=p)
+            dd.backend.sync_compute()
+            self.x = d  # the loops below update self.x
+            try:
+                if self.M is not None:
+                    inner = self._iterate_preconditioned(limit, bb, residuals, max_iter - its,
+                                                         overlap)
+                else:
+                    inner = self._iterate_plain(rr, limit, bb, residuals, max_iter - its, overlap)
+            finally:
+                self.x = x
+            dd.axpby(1.0, x, 1.0, d, out=x)
+            dd.backend.sync_compute()
+            its, residuals = its + inner.iterations, list(inner.residuals)
+            if not inner.converged:
+                return CGResult(False, its, residuals, inner.reason)
+
+    def _solve(self, tol, max_iter, x0_zero, overlap) -> CGResult:
         dd, x, b, r, p = self.dd, self.x, self.b, self.r, self.p
         self.phase_times = {k: 0.0 for k in self.phase_times}
         if not x0_zero and self.group_x is None:
@@ -210,6 +314,11 @@ class ConjugateGradient:
             return CGResult(True, 0, residuals, "converged")
         if self.M is not None:
             return self._iterate_preconditioned(limit, bb, residuals, max_iter, overlap)
+        return self._iterate_plain(rr, limit, bb, residuals, max_iter, overlap)
+
+    def _iterate_plain(self, rr, limit, bb, residuals, max_iter, overlap) -> CGResult:
+        """the plain loop from p = r, rr = r . r; updates self.x"""
+        dd, x, r, p = self.dd, self.x, self.r, self.p
         for it in range(1, max_iter + 1):
             t0 = time.perf_counter()
             self._apply(p, self.group_p, overlap)

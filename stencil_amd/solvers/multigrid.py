@@ -23,9 +23,22 @@ The cycle never calls swap(): A e lives in the next buffer of e. There are
 no reductions, so every rank takes identical branches. Levels >= 1 run
 non-overlapped; level 0 honours `overlap`.
 
+Variable coefficients. When operator_at(0) is a DiffusionOperator
+(solvers/diffusion.py: sigma I - div(k grad), k a quantity), the hierarchy
+is built from it and operator_at is not asked for the levels below. A coarse
+level then has four quantities e, f, k, d in the exchange groups [[e], [k]]:
+k is the mean of its 8 children (grid_restrict, no new transfer operator;
+CLAMP on non-periodic faces, exchanged once), the spacing is doubled, sigma
+unchanged, and d = omega / diag per cell (diffusion_inv_diagonal) takes the
+place of w: the sweep is e = e + d (f - next[e]), one scaled_update, the
+first sweep e = d f. Level 0 uses the operator's dinv quantity for d.
+refresh_coefficients() redoes restriction, exchanges and diagonals after k
+changed. The constant-coefficient path is the one above, unchanged.
+
 Not there: a whole-cycle hipGraph (each level costs host launches and
 syncs, see phase_times), agglomeration of coarse levels onto fewer GPUs,
-trilinear transfer, variable coefficients.
+trilinear transfer, Galerkin coarse operators, harmonic-mean or
+user-supplied face coefficients.
 """
 from __future__ import annotations
 
@@ -35,10 +48,11 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
-from ..boundary import FACES
+from ..boundary import FACES, Boundary
 from ..core import DataHandle, DistributedDomain, Next
 from ..stencil import Stencil
 from .cg import check_boundary, check_operator
+from .diffusion import DiffusionOperator
 from .transfer import GridTransfer
 
 
@@ -46,8 +60,16 @@ class _Level:
     __slots__ = ("dd", "A", "w", "e", "f", "group", "transfer")
 
     def __init__(self, dd, A, w, e, f, group):
+        # A: a Stencil (w = omega / its centre weight) or a DiffusionOperator
+        # (w is None: the per-cell omega / diag lives in the quantity A.dinv)
         self.dd, self.A, self.w, self.e, self.f, self.group = dd, A, w, e, f, group
         self.transfer: Optional[GridTransfer] = None  # to the next coarser level
+
+    def apply(self, where):
+        if self.w is None:
+            self.A.apply(self.e, where=where)
+        else:
+            self.dd.apply_stencil(self.A, self.e, where=where)
 
 
 def _centre(who: str, A: Stencil) -> float:
@@ -74,7 +96,10 @@ class GeometricMultigrid:
                  e: DataHandle, group_e: int, nu: int = 2, omega: float = 2.0 / 3.0,
                  coarse_sweeps: int = 8, max_levels: Optional[int] = None):
         """dd is realized. operator_at(level) is the operator at spacing x
-        2^level; level 0 must be the operator CG solves with. e is the
+        2^level; level 0 must be the operator CG solves with. When
+        operator_at(0) is a DiffusionOperator (it needs a dinv quantity:
+        ValueError without), the levels below are built from its
+        coefficient and operator_at is not called again. e is the
         quantity of dd the cycle writes (CG's z), group_e its exchange
         group. nu sweeps before and after each coarse-grid correction,
         coarse_sweeps on the last level, damping omega.
@@ -112,9 +137,15 @@ class GeometricMultigrid:
         check_boundary(who, dd, (e,))
         self.omega, self.nu, self.coarse_sweeps = float(omega), int(nu), int(coarse_sweeps)
         self.overlap = True  # of level 0; Poisson3D.solve sets it
-        self._levels: List[_Level] = [
-            _Level(dd, A0, self.omega / _centre(who, A0), e, None, group_e)
-        ]
+        self._variable = isinstance(A0, DiffusionOperator)
+        if self._variable:
+            if A0.dinv is None:
+                raise ValueError(f"{who}: the DiffusionOperator of level 0 has no dinv quantity")
+            if A0.k.dtype != dt:
+                raise ValueError(f"{who}: the coefficient is {A0.k.dtype}, e is {dt}")
+            self._levels: List[_Level] = [_Level(dd, A0, None, e, None, group_e)]
+        else:
+            self._levels = [_Level(dd, A0, self.omega / _centre(who, A0), e, None, group_e)]
         while max_levels is None or len(self._levels) < max_levels:
             nxt = self._coarsen(who, self._levels[-1], operator_at, len(self._levels), dt)
             if nxt is None:
@@ -127,6 +158,8 @@ class GeometricMultigrid:
                 "subdomains at least max(2, radius) wide)"
             )
         self.levels = [tuple(lv.dd.size) for lv in self._levels]
+        if self._variable:
+            self.refresh_coefficients()
         # host wall time per level of all cycles since reset_times(): each
         # level's share ends in a host sync
         self.phase_times = {}
@@ -145,22 +178,33 @@ class GeometricMultigrid:
         subs = list(_subdomains(fdd))
         if any(c % 2 for _, o, s in subs for c in o + s):
             return None
-        A = operator_at(level)
-        if not A.is_symmetric():
-            raise ValueError(f"{who}: the stencil of level {level} is not symmetric")
-        w = self.omega / _centre(who, A)
-        need = tuple(max(2, r) for r in _face_radius(A))
+        if self._variable:
+            # built from the fine level's operator: operator_at is not asked
+            A, w, need, radius = None, None, (2, 2, 2), fine.A.radius()
+        else:
+            A = operator_at(level)
+            if not A.is_symmetric():
+                raise ValueError(f"{who}: the stencil of level {level} is not symmetric")
+            w = self.omega / _centre(who, A)
+            need = tuple(max(2, r) for r in _face_radius(A))
+            radius = A.radius()
         if any(s[a] // 2 < need[a] for _, _, s in subs for a in range(3)):
             return None
         cdd = DistributedDomain(*(n // 2 for n in fdd.size), backend=fdd.backend_kind,
                                 device=fdd.torch_device)
-        cdd.set_radius(A.radius())
+        cdd.set_radius(radius)
         cdd.set_placement(fdd.strategy)
         cdd.set_methods(fdd.methods)
         cdd.set_gpus(fdd.gpus)
         e = cdd.add_data(dt, "e")
         f = cdd.add_data(dt, "f")
-        cdd.set_exchange_groups([[e.index]])
+        k = d = None
+        if self._variable:
+            k = cdd.add_data(dt, "k")
+            d = cdd.add_data(dt, "d")
+            cdd.set_exchange_groups([[e.index], [k.index]])
+        else:
+            cdd.set_exchange_groups([[e.index]])
         spec = fdd.boundary
         if spec is not None:
             for a in range(3):
@@ -170,6 +214,8 @@ class GeometricMultigrid:
                     kind = spec.kind(fine.e.index, a, s)
                     value = spec.value(fine.e.index, a, s)
                     cdd.set_boundary(FACES[2 * a + s], kind, 0 if value is None else value)
+                    if k is not None:
+                        cdd.set_boundary(FACES[2 * a + s], Boundary.CLAMP, quantities=[k])
         cpl, fpl = cdd.do_placement(), fdd.placement
         if tuple(cpl.dim()) != tuple(fpl.dim()):
             return None
@@ -182,7 +228,28 @@ class GeometricMultigrid:
                 return None
         cdd.realize()
         fine.transfer = GridTransfer(fdd, cdd)
+        if self._variable:
+            # doubled spacing, the same sigma; k and d are filled by
+            # refresh_coefficients()
+            A = DiffusionOperator(cdd, k, 1, spacing=tuple(2.0 * s for s in fine.A.spacing),
+                                  sigma=fine.A.sigma, dinv=d)
         return _Level(cdd, A, w, e, f, 0)
+
+    def refresh_coefficients(self):
+        """after the coefficient k of level 0 changed (DiffusionOperator
+        hierarchies only): exchange k, restrict it level by level (the mean
+        of the 8 children, then one exchange) and recompute every level's
+        d = omega / diag."""
+        if not self._variable:
+            raise ValueError("GeometricMultigrid.refresh_coefficients: the hierarchy was built "
+                             "from constant-coefficient stencils")
+        for l, lv in enumerate(self._levels):
+            if l > 0:
+                fine = self._levels[l - 1]
+                fine.transfer.restrict(1.0, fine.A.k, 0.0, fine.A.k, lv.A.k)
+            lv.A.refresh()
+            lv.A.inv_diagonal(self.omega, lv.A.dinv)
+            lv.dd.backend.sync_compute()
 
     # ---- the cycle ----
     def apply(self, f: DataHandle, e: DataHandle):
@@ -200,17 +267,20 @@ class GeometricMultigrid:
         dd = lv.dd
         dd.backend.sync_compute()  # the exchange reads e on other streams
         if overlap:
-            dd.apply_stencil(lv.A, lv.e, where="interior")
+            lv.apply("interior")
             dd.exchange(lv.group)
-            dd.apply_stencil(lv.A, lv.e, where="exterior")
+            lv.apply("exterior")
             dd.backend.sync_compute()  # the exterior slabs ran on stream 1
         else:
             dd.exchange(lv.group)
-            dd.apply_stencil(lv.A, lv.e, where="all")
+            lv.apply("all")
 
     def _sweep(self, lv: _Level, f: DataHandle, overlap: bool):
         self._operator(lv, overlap)
-        lv.dd.axpbypcz(1.0, lv.e, lv.w, f, -lv.w, Next(lv.e), out=lv.e)
+        if lv.w is None:
+            lv.dd.scaled_update(1.0, lv.e, lv.A.dinv, 1.0, f, -1.0, Next(lv.e), out=lv.e)
+        else:
+            lv.dd.axpbypcz(1.0, lv.e, lv.w, f, -lv.w, Next(lv.e), out=lv.e)
 
     def _cycle(self, l: int, f: DataHandle):
         lv = self._levels[l]
@@ -218,7 +288,10 @@ class GeometricMultigrid:
         overlap = self.overlap and l == 0
         key = f"level{l}"
         t0 = time.perf_counter()
-        lv.dd.axpby(lv.w, f, 0.0, f, out=lv.e)
+        if lv.w is None:
+            lv.dd.scaled_update(0.0, f, lv.A.dinv, 1.0, f, 0.0, f, out=lv.e)
+        else:
+            lv.dd.axpby(lv.w, f, 0.0, f, out=lv.e)
         for _ in range((self.coarse_sweeps if last else self.nu) - 1):
             self._sweep(lv, f, overlap)
         if not last:

@@ -404,6 +404,107 @@ class TorchBackend:
                           for c in (alpha, beta, gamma))
             tout.copy_(al * tx + be * ty + ga * tz)
 
+    def field_scaled_update(self, boxes, alpha, x, x_next, d, d_next, beta, y, y_next, gamma, z,
+                            z_next, out, out_next, stream_id=0):
+        """out = alpha * x + d * (beta * y + gamma * z) in the quantity's
+        type, the coefficients rounded to it once; no FMA"""
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_scaled_update", li, lo, hi,
+                                   [(x, x_next), (d, d_next), (y, y_next), (z, z_next),
+                                    (out, out_next)])
+            if v is None:
+                continue
+            tx, td, ty, tz, tout = v
+            al, be, ga = (torch.tensor(c, dtype=tx.dtype, device=tx.device)
+                          for c in (alpha, beta, gamma))
+            tout.copy_(al * tx + td * (be * ty + ga * tz))
+
+    # ---- variable-coefficient diffusion: slicing references of
+    # csrc/src/diffusion_op.hip, written from the operator's definition ----
+    def _diffusion_views(self, op, li, qis, lo, hi, stream_id):
+        """(dom, pos, ext) of the validated global box, None when empty; the
+        native ops' checks, as ValueErrors"""
+        if not 0 <= li < len(self.domains):
+            raise ValueError(f"{op}: no such domain {li}")
+        dom = self.domains[li]
+        for qi in qis:
+            if not 0 <= qi < len(dom.elem_sizes):
+                raise ValueError(f"{op}: no such quantity")
+        sizes = {dom.elem_sizes[qi] for qi in qis}
+        if not sizes <= {4, 8}:
+            raise ValueError(f"{op}: float32/float64 quantities only")
+        if len(sizes) != 1:
+            raise ValueError(f"{op}: quantities differ in element size")
+        if stream_id not in (0, 1):
+            raise ValueError(f"{op}: stream id must be 0 or 1")
+        ext = tuple(hi[i] - lo[i] for i in range(3))
+        if min(ext) <= 0:
+            return None
+        flo, raw = dom.full_lo(), dom.raw_size()
+        pos = tuple(lo[i] - flo[i] for i in range(3))
+        if any(pos[i] < 0 or pos[i] + ext[i] > raw[i] for i in range(3)):
+            raise ValueError(f"{op}: region {lo}..{hi} is outside the allocation")
+        if any(pos[i] < 1 or pos[i] + ext[i] + 1 > raw[i] for i in range(3)):
+            raise ValueError(f"{op}: the 1-cell face apron of region {lo}..{hi} leaves the "
+                             "allocation")
+        return dom, pos, ext
+
+    @staticmethod
+    def _face_neighbours(dom, t, pos, ext):
+        """[(axis, view of t shifted by -1, by +1)] for axis x, y, z"""
+        out = []
+        for a in range(3):
+            lo_p, hi_p = list(pos), list(pos)
+            lo_p[a] -= 1
+            hi_p[a] += 1
+            out.append((a, t[dom._sl(lo_p, ext)], t[dom._sl(hi_p, ext)]))
+        return out
+
+    def diffusion_apply(self, li, src_qi, k_qi, dst_qi, lo, hi, h, sigma, dtype, stream_id=0):
+        """next[dst_qi] = sigma u + sum over the six faces of
+        h_a * 0.5 (k + k') * (u - u'), u = curr[src_qi], k = curr[k_qi], in
+        the quantity's type (h and sigma rounded to it once)"""
+        import numpy as np
+
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"diffusion_apply supports float32/float64, got {dt}")
+        v = self._diffusion_views("diffusion_apply", li, (src_qi, k_qi, dst_qi), lo, hi, stream_id)
+        if self.domains[li].elem_sizes[k_qi] != dt.itemsize:
+            raise ValueError("diffusion_apply: element size of the quantities does not match "
+                             "the type")
+        if v is None:
+            return
+        dom, pos, ext = v
+        u, k = dom.curr[src_qi], dom.curr[k_qi]
+        tdt = u.dtype
+        uc, kc = u[dom._sl(pos, ext)], k[dom._sl(pos, ext)]
+        half = torch.tensor(0.5, dtype=tdt)
+        acc = torch.tensor(sigma, dtype=tdt) * uc
+        for (a, um, up), (_, km, kp) in zip(self._face_neighbours(dom, u, pos, ext),
+                                            self._face_neighbours(dom, k, pos, ext)):
+            ha = torch.tensor(h[a], dtype=tdt)
+            acc = acc + ha * (half * (kc + km)) * (uc - um)
+            acc = acc + ha * (half * (kc + kp)) * (uc - up)
+        dom.next[dst_qi][dom._sl(pos, ext)] = acc
+
+    def diffusion_inv_diagonal(self, li, k_qi, out_qi, out_next, lo, hi, h, sigma, omega,
+                               stream_id=0):
+        """out = omega / (sigma + sum over the six faces of h_a * 0.5 (k + k'))"""
+        v = self._diffusion_views("diffusion_inv_diagonal", li, (k_qi, out_qi), lo, hi, stream_id)
+        if v is None:
+            return
+        dom, pos, ext = v
+        k = dom.curr[k_qi]
+        tdt = k.dtype
+        kc = k[dom._sl(pos, ext)]
+        half = torch.tensor(0.5, dtype=tdt)
+        diag = torch.full_like(kc, sigma)
+        for a, km, kp in self._face_neighbours(dom, k, pos, ext):
+            ha = torch.tensor(h[a], dtype=tdt)
+            diag = diag + ha * (half * (kc + km)) + ha * (half * (kc + kp))
+        dom.region(out_qi, pos, ext, out_next).copy_(torch.tensor(omega, dtype=tdt) / diag)
+
     # ---- grid transfer: slicing references of csrc/src/grid_transfer.hip ----
     def device_of(self, li):
         return self.domains[li].device
