@@ -25,6 +25,15 @@ coefficient_field); --precond jacobi is the diagonal preconditioner it makes
 possible. The record then holds coefficient (and contrast), and --kernels
 adds diffusion_apply (3 passes: u, k, out) and scaled_update (5 passes, in
 place). Without --coefficient the output is what it was.
+
+--nullspace constant solves the singular problem (--sigma 0 with --boundary
+periodic or mirror) with the solver's projection off the constants; the
+record then holds nullspace, and corrections, the number of correction
+solves the true-residual check asked for. --kernels also times each kernel
+of the projection against the existing kernel of equal traffic, alternated
+old, new, old, new in one process: dot_sums : dot, cg_update_sum :
+cg_update, axpbyc : axpby (the *_pair_ms lists, and *_ratio = new / old of
+the means).
 """
 import argparse
 import json
@@ -82,7 +91,12 @@ def main():
     ap.add_argument("--contrast", type=float, default=16.0, help="the high value of 'jump'")
     ap.add_argument("--tol", type=float, default=0.0,
                     help="0: exactly --iters iterations; > 0: solve to this tolerance")
+    ap.add_argument("--nullspace", default="none", choices=["none", "constant"],
+                    help="constant: the singular problem, --sigma 0 --boundary periodic|mirror")
     args = ap.parse_args()
+    if args.nullspace == "constant" and not (
+            args.sigma == 0.0 and args.boundary in ("periodic", "mirror")):
+        ap.error("--nullspace constant needs --sigma 0 and --boundary periodic or mirror")
 
     dtype = np.float32 if args.dtype == "f32" else np.float64
     gpus = list(range(args.gpus)) if args.backend == "native" else [0] * args.gpus
@@ -90,7 +104,8 @@ def main():
     app = Poisson3D(size, order=args.order, dtype=dtype, sigma=args.sigma, backend=args.backend,
                     gpus=gpus, boundary=_BOUNDARIES[args.boundary],
                     preconditioner={"none": None, "mg": "multigrid", "jacobi": "jacobi"}[args.precond],
-                    coefficient=args.coefficient != "none")
+                    coefficient=args.coefficient != "none",
+                    nullspace=None if args.nullspace == "none" else args.nullspace)
     app.realize()
     dd = app.dd
     if args.coefficient in ("smooth", "jump"):
@@ -142,6 +157,9 @@ def main():
             out["contrast"] = args.contrast
         if app.jacobi is not None:
             out["precond_ms"] = ph["precond"] / n * 1e3
+    if args.nullspace != "none":
+        out["nullspace"] = args.nullspace
+        out["corrections"] = app.cg.corrections
     if args.tol > 0:
         out["iterations"] = res.iterations
         out["converged"] = res.converged
@@ -196,6 +214,19 @@ def main():
                           sync=coarse.dd.backend.sync))
             report("grid_prolong_add", 2.125,
                    window(lambda: top.transfer.prolong_add(coarse.f, z)))
+
+        # the projection's kernels against the kernels of equal traffic,
+        # alternated old, new, old, new so that drift hits both alike
+        def pair(name, old, new):
+            ts = [window(old), window(new), window(old), window(new)]
+            out[f"{name}_pair_ms"] = ts
+            out[f"{name}_ratio"] = (ts[1] + ts[3]) / (ts[0] + ts[2])
+
+        pair("dot_sums", lambda: dd.dot(p, sa.Next(p)), lambda: dd.dot_sums(p, sa.Next(p)))
+        pair("cg_update_sum", lambda: dd.cg_update(1e-30, x, p, r),
+             lambda: dd.cg_update_sum(1e-30, x, p, r))
+        pair("axpbyc", lambda: dd.axpby(1.0, r, 0.5, p, out=p),
+             lambda: dd.axpbyc(1.0, r, 0.5, p, 1e-30, out=p))
         t = time.perf_counter()
         for _ in range(k):
             dd.backend.sync_compute()

@@ -252,13 +252,17 @@ public:
   //// scratch of the field reductions (csrc/src/vector_ops.hip): per
   //// domain, one device array of per-block partial sums and a pinned host
   //// landing buffer of the same size, allocated on first use and freed
-  //// with the engine. One reduction per domain may be in flight.
+  //// with the engine: kReduceValues * kReducePartials doubles each, value
+  //// v of block b of `count` blocks at [v * count + b]. One reduction per
+  //// domain may be in flight.
   static constexpr int kReducePartials = 4096; // the reductions' grid cap
+  static constexpr int kReduceValues = 3;      // values one reduction returns, at most
   struct ReduceScratch {
     double *dev = nullptr;
     double *host = nullptr;
     hipStream_t stream = nullptr; // stream of the reduction in flight
-    int count = 0;                // its number of partials (0: empty region)
+    int count = 0;                // its number of partials per value (0: empty region)
+    int values = 1;               // its number of values; 1 whenever none is in flight
     bool pending = false;
   };
   // allocate = false: the bookkeeping only (an empty region launches nothing)

@@ -1,6 +1,7 @@
 // App compute ops (launched on a domain's compute stream).
 #pragma once
 
+#include <array>
 #include <memory>
 
 #include "stencil_amd/core.hpp"
@@ -201,8 +202,50 @@ double cg_update(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t 
                  const Rect3 &region, int streamId = 0);
 void cg_update_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
                      const Rect3 &region, int streamId = 0);
-// wait for the reduction begun on `dom` and return its value
+// wait for the reduction begun on `dom` and return its value. For the
+// one-valued ops; std::runtime_error (the reduction stays in flight) when
+// the one in flight has more values.
 double reduction_end(ExchangeEngine &eng, int dom);
+
+// The reductions of singular problems: the projection v - mean(v) onto the
+// complement of the constant null space, fused into passes a Krylov
+// iteration makes anyway. The contract, the walks, the validation and the
+// determinism of the ops above; a reduction with several values writes one
+// partial per block AND value (the scratch holds kReduceValues *
+// kReducePartials doubles, value-major) and the host sums each value's
+// partials in index order. The launch shapes are those of the ops above.
+//
+// sum over region of a(p), in fp64: one read pass
+double field_sum(ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
+                 int streamId = 0);
+void field_sum_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
+                     int streamId = 0);
+// (sum a * b, sum a, sum b) from ONE pass over a and b, field_dot's traffic;
+// products and sums in fp64. a and b may be the same buffer.
+std::array<double, 3> field_dot_sums(ExchangeEngine &eng, int dom, int64_t a, bool aNext,
+                                     int64_t b, bool bNext, const Rect3 &region,
+                                     int streamId = 0);
+void field_dot_sums_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b,
+                          bool bNext, const Rect3 &region, int streamId = 0);
+// cg_update (the same arithmetic, the same single rounding of alpha; x, p
+// and r distinct) returning (sum r_new^2, sum r_new): cg_update's traffic
+std::array<double, 2> cg_update_sum(ExchangeEngine &eng, int dom, double alpha, int64_t x,
+                                    int64_t p, int64_t r, const Rect3 &region, int streamId = 0);
+void cg_update_sum_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p,
+                         int64_t r, const Rect3 &region, int streamId = 0);
+// out = alpha * x + beta * y + c in the quantity's type (alpha, beta and c
+// rounded to it once at launch; FMA contraction and association
+// unspecified, as for field_axpby). out may be the buffer of x or of y.
+// field_axpby's traffic.
+void field_axpbyc(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
+                  int64_t y, bool yNext, double c, int64_t out, bool outNext,
+                  const Rect3 &region, int streamId = 0);
+// wait for the n-valued reduction begun on `dom` and write its values to
+// out[0..n): n = 1 field_sum (and the one-valued ops above), 2
+// cg_update_sum, 3 field_dot_sums. std::runtime_error, the reduction
+// staying in flight, when the one in flight has another value count;
+// std::invalid_argument for n outside 1..kReduceValues or a null out.
+void reduction_end_n(ExchangeEngine &eng, int dom, double *out, int n);
 
 // Grid transfer between a fine and a coarse local domain on cell-centred
 // 2:1 coarsening (csrc/src/grid_transfer.hip): coarse cell c has the 8 fine

@@ -501,6 +501,95 @@ PYBIND11_MODULE(_C, m) {
         return value_errors([&] { return reduction_end(eng, dom); });
       },
       py::arg("eng"), py::arg("dom"));
+  // the reductions of singular problems: several values from one pass
+  m.def(
+      "field_sum",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
+                     int streamId) {
+        return value_errors([&] { return field_sum(eng, dom, a, aNext, region, streamId); });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("region"),
+      py::arg("stream_id") = 0);
+  m.def(
+      "field_sum_begin",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
+                     int streamId) {
+        value_errors([&] {
+          field_sum_begin(eng, dom, a, aNext, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("region"),
+      py::arg("stream_id") = 0);
+  m.def(
+      "field_dot_sums",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                     const Rect3 &region, int streamId) {
+        const std::array<double, 3> v = value_errors(
+            [&] { return field_dot_sums(eng, dom, a, aNext, b, bNext, region, streamId); });
+        return py::make_tuple(v[0], v[1], v[2]);
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "field_dot_sums_begin",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_dot_sums_begin(eng, dom, a, aNext, b, bNext, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "cg_update_sum",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
+                     const Rect3 &region, int streamId) {
+        const std::array<double, 2> v = value_errors(
+            [&] { return cg_update_sum(eng, dom, alpha, x, p, r, region, streamId); });
+        return py::make_tuple(v[0], v[1]);
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "cg_update_sum_begin",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          cg_update_sum_begin(eng, dom, alpha, x, p, r, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "field_axpbyc",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                     double beta, int64_t y, bool yNext, double c, int64_t out, bool outNext,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_axpbyc(eng, dom, alpha, x, xNext, beta, y, yNext, c, out, outNext, region,
+                       streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
+      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("c"), py::arg("out"),
+      py::arg("out_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "reduction_end_n",
+      [value_errors](ExchangeEngine &eng, int dom, int n) {
+        std::array<double, ExchangeEngine::kReduceValues> v{};
+        value_errors([&] {
+          reduction_end_n(eng, dom, v.data(), n);
+          return 0;
+        });
+        py::tuple out(n);
+        for (int i = 0; i < n; ++i) out[i] = v[i];
+        return out;
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("n"));
 
   // Whole-step replay graphs: opaque owning objects. A live graph keeps its
   // engine (and through it the domains) alive; dropping the last reference

@@ -605,8 +605,9 @@ ExchangeEngine::ReduceScratch &ExchangeEngine::reduce_scratch(int dom, bool allo
   ReduceScratch &r = reduce_.at(dom);
   if (allocate && !r.dev) {
     STENCIL_HIP(hipSetDevice(domains_[dom]->gpu()));
-    STENCIL_HIP(hipMalloc((void **)&r.dev, kReducePartials * sizeof(double)));
-    STENCIL_HIP(hipHostMalloc((void **)&r.host, kReducePartials * sizeof(double), 0));
+    const size_t bytes = (size_t)kReduceValues * kReducePartials * sizeof(double);
+    STENCIL_HIP(hipMalloc((void **)&r.dev, bytes));
+    STENCIL_HIP(hipHostMalloc((void **)&r.host, bytes, 0));
   }
   return r;
 }

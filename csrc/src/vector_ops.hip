@@ -3,6 +3,10 @@
 // scaled out = alpha x + d (beta y + gamma z), and the fused
 // conjugate-gradient update. Pure
 // streaming kernels: every cell of the region is read (and written) once.
+// For singular problems (the constant null space, solvers/cg.py) also the
+// sum of a field, the inner product together with both sums, the fused
+// update together with sum r_new, and out = alpha x + beta y + c: the
+// projection v - mean(v) rides on passes the iteration makes anyway.
 //
 // Contract (the stencil operator's): nothing outside `region` is written
 // in any buffer, and no cell outside it enters the arithmetic. Unlike the
@@ -22,11 +26,14 @@
 // Reductions are deterministic: fp64 accumulation per thread, cross-lane
 // shuffles per wave, LDS per block, one partial per block written with an
 // ordinary store, the partials summed in index order on the host. No
-// atomics. The grid never exceeds ExchangeEngine::kReducePartials blocks,
-// the size of the engine's per-domain scratch.
+// atomics. The grid never exceeds ExchangeEngine::kReducePartials blocks;
+// the engine's per-domain scratch holds kReduceValues times as many
+// doubles, value-major (partials[v * blocks + b]), for the reductions that
+// return up to three values from one pass.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <initializer_list>
 #include <stdexcept>
 #include <string>
@@ -145,6 +152,41 @@ __device__ __forceinline__ void block_sum_store(double v, double *partials) {
   }
 }
 
+// acc += a in fp64, component after component
+__device__ __forceinline__ void add_val(double &acc, float a) { acc += (double)a; }
+__device__ __forceinline__ void add_val(double &acc, double a) { acc += a; }
+__device__ __forceinline__ void add_val(double &acc, F4 a) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) add_val(acc, a[c]);
+}
+__device__ __forceinline__ void add_val(double &acc, D2 a) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c) add_val(acc, a[c]);
+}
+
+// block_sum_store for NV values at once: value v of block b lands in
+// partials[v * blocks + b]. The same fixed order per value.
+template <int NV>
+__device__ __forceinline__ void block_store_sums(const double (&in)[NV], double *partials) {
+  __shared__ double sWaves[NV][4];
+  const int tid = threadIdx.y * blockDim.x + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    double v = in[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((tid & 63) == 0) sWaves[k][tid >> 6] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int64_t blocks = (int64_t)gridDim.z * gridDim.y * gridDim.x;
+    const int64_t b = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+      partials[k * blocks + b] = ((sWaves[k][0] + sWaves[k][1]) + sWaves[k][2]) + sWaves[k][3];
+  }
+}
+
 struct DotF {
   const char *a, *b;
   double acc;
@@ -199,6 +241,52 @@ template <typename T> struct CgF {
   }
 };
 
+struct SumF {
+  const char *a;
+  double acc;
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    add_val(acc, *(const V *)(a + off));
+  }
+};
+
+struct DotSumsF {
+  const char *a, *b;
+  double ab, sa, sb;
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V va = *(const V *)(a + off), vb = *(const V *)(b + off);
+    add_prod(ab, va, vb);
+    add_val(sa, va);
+    add_val(sb, vb);
+  }
+};
+
+// CgF's arithmetic, statement for statement, plus sum r_new
+template <typename T> struct CgSumF {
+  char *x, *r;
+  const char *p, *ap;
+  T alpha;
+  double acc, sum;
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vp = *(const V *)(p + off), vap = *(const V *)(ap + off);
+    const V vx = *(const V *)(x + off), vr = *(const V *)(r + off);
+    const V rn = vr - alpha * vap;
+    *(V *)(x + off) = vx + alpha * vp;
+    *(V *)(r + off) = rn;
+    add_prod(acc, rn, rn);
+    add_val(sum, rn);
+  }
+};
+
+template <typename T> struct AxpbycF {
+  const char *x, *y;
+  char *out;
+  T alpha, beta, c;
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vx = *(const V *)(x + off), vy = *(const V *)(y + off);
+    *(V *)(out + off) = alpha * vx + beta * vy + c;
+  }
+};
+
 template <typename T, bool STRIPS>
 __global__ void __launch_bounds__(256)
     dot_kernel(Geom g, const char *a, const char *b, double *partials) {
@@ -237,6 +325,45 @@ __global__ void __launch_bounds__(256)
   CgF<T> f{x, r, p, ap, alpha, 0.0};
   walk<T, STRIPS>(g, f);
   block_sum_store(f.acc, partials);
+}
+
+template <typename T, bool STRIPS>
+__global__ void __launch_bounds__(256) sum_kernel(Geom g, const char *a, double *partials) {
+  SumF f{a, 0.0};
+  walk<T, STRIPS>(g, f);
+  const double v[1] = {f.acc};
+  block_store_sums<1>(v, partials);
+}
+
+// float: the 4 x unrolled strip loop wants 74 VGPRs to keep its 8 loads in
+// flight. Held to 64 (8 waves per SIMD) the scheduler serialises them, 2 in
+// flight, and the kernel runs 5-6% behind dot_kernel; at 6 waves it batches
+// them as dot_kernel does. double fits 8 waves as it is.
+template <typename T, bool STRIPS>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 6 : 8, sizeof(T) == 4 ? 6 : 8)))
+    dot_sums_kernel(Geom g, const char *a, const char *b, double *partials) {
+  DotSumsF f{a, b, 0.0, 0.0, 0.0};
+  walk<T, STRIPS>(g, f);
+  const double v[3] = {f.ab, f.sa, f.sb};
+  block_store_sums<3>(v, partials);
+}
+
+template <typename T, bool STRIPS>
+__global__ void __launch_bounds__(256)
+    cg_update_sum_kernel(Geom g, char *x, const char *p, const char *ap, char *r, T alpha,
+                         double *partials) {
+  CgSumF<T> f{x, r, p, ap, alpha, 0.0, 0.0};
+  walk<T, STRIPS>(g, f);
+  const double v[2] = {f.acc, f.sum};
+  block_store_sums<2>(v, partials);
+}
+
+template <typename T, bool STRIPS>
+__global__ void __launch_bounds__(256)
+    axpbyc_kernel(Geom g, const char *x, const char *y, char *out, T alpha, T beta, T c) {
+  AxpbycF<T> f{x, y, out, alpha, beta, c};
+  walk<T, STRIPS>(g, f);
 }
 
 //// host ////
@@ -360,6 +487,22 @@ void land_partials(ExchangeEngine::ReduceScratch &sc, int blocks, hipStream_t st
   sc.pending = true;
 }
 
+// the n-valued form: value-major partials, n * blocks doubles in one copy
+void land_partials_n(ExchangeEngine::ReduceScratch &sc, int blocks, int n, hipStream_t stream) {
+  STENCIL_HIP(hipMemcpyAsync(sc.host, sc.dev, (size_t)n * (size_t)blocks * sizeof(double),
+                             hipMemcpyDeviceToHost, stream));
+  sc.stream = stream;
+  sc.count = blocks;
+  sc.values = n;
+  sc.pending = true;
+}
+
+void land_empty_n(ExchangeEngine::ReduceScratch &sc, int n) {
+  sc.count = 0;
+  sc.values = n;
+  sc.pending = true;
+}
+
 } // namespace
 
 void field_dot_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
@@ -415,6 +558,10 @@ double reduction_end(ExchangeEngine &eng, int dom) {
   if (!sc.pending)
     throw std::runtime_error("reduction_end: no reduction in flight on domain " +
                              std::to_string(dom));
+  if (sc.values != 1)
+    throw std::runtime_error("reduction_end: the reduction in flight on domain " +
+                             std::to_string(dom) + " has " + std::to_string(sc.values) +
+                             " values (call reduction_end_n)");
   sc.pending = false;
   if (sc.count == 0) return 0.0;
   STENCIL_HIP(hipSetDevice(eng.domain(dom).gpu()));
@@ -422,6 +569,129 @@ double reduction_end(ExchangeEngine &eng, int dom) {
   double sum = 0.0;
   for (int i = 0; i < sc.count; ++i) sum += sc.host[i]; // index order
   return sum;
+}
+
+void reduction_end_n(ExchangeEngine &eng, int dom, double *out, int n) {
+  if (dom < 0 || dom >= eng.num_domains())
+    throw std::invalid_argument("reduction_end_n: no such domain " + std::to_string(dom));
+  if (out == nullptr || n < 1 || n > ExchangeEngine::kReduceValues)
+    throw std::invalid_argument("reduction_end_n: want 1.." +
+                                std::to_string(ExchangeEngine::kReduceValues) + " values, got " +
+                                std::to_string(n));
+  ExchangeEngine::ReduceScratch &sc = eng.reduce_scratch(dom, false);
+  if (!sc.pending)
+    throw std::runtime_error("reduction_end_n: no reduction in flight on domain " +
+                             std::to_string(dom));
+  if (sc.values != n)
+    throw std::runtime_error("reduction_end_n: the reduction in flight on domain " +
+                             std::to_string(dom) + " has " + std::to_string(sc.values) +
+                             " values, not " + std::to_string(n));
+  sc.pending = false;
+  sc.values = 1; // what the one-valued ops leave untouched
+  for (int v = 0; v < n; ++v) out[v] = 0.0;
+  if (sc.count == 0) return;
+  STENCIL_HIP(hipSetDevice(eng.domain(dom).gpu()));
+  STENCIL_HIP(hipStreamSynchronize(sc.stream));
+  for (int v = 0; v < n; ++v) {
+    const double *part = sc.host + (size_t)v * (size_t)sc.count;
+    double sum = 0.0;
+    for (int i = 0; i < sc.count; ++i) sum += part[i]; // index order
+    out[v] = sum;
+  }
+}
+
+void field_sum_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
+                     int streamId) {
+  const Launch l = plan_launch("field_sum", eng, dom, {{a, aNext}}, region);
+  ExchangeEngine::ReduceScratch &sc = begin_reduction("field_sum", eng, dom, !l.empty);
+  if (l.empty) return land_empty_n(sc, 1);
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  if (l.es == 4)
+    VEC_OPS_LAUNCH(float, l, sum_kernel, stream, l.g, (const char *)l.ptr[0], sc.dev);
+  else
+    VEC_OPS_LAUNCH(double, l, sum_kernel, stream, l.g, (const char *)l.ptr[0], sc.dev);
+  land_partials_n(sc, l.blocks, 1, stream);
+}
+
+void field_dot_sums_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b,
+                          bool bNext, const Rect3 &region, int streamId) {
+  const Launch l = plan_launch("field_dot_sums", eng, dom, {{a, aNext}, {b, bNext}}, region);
+  ExchangeEngine::ReduceScratch &sc = begin_reduction("field_dot_sums", eng, dom, !l.empty);
+  if (l.empty) return land_empty_n(sc, 3);
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  if (l.es == 4)
+    VEC_OPS_LAUNCH(float, l, dot_sums_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], sc.dev);
+  else
+    VEC_OPS_LAUNCH(double, l, dot_sums_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], sc.dev);
+  land_partials_n(sc, l.blocks, 3, stream);
+}
+
+void cg_update_sum_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p,
+                         int64_t r, const Rect3 &region, int streamId) {
+  // operands: curr[x], curr[p], next[p] (= A p), curr[r]
+  const Launch l = plan_launch("cg_update_sum", eng, dom,
+                               {{x, false}, {p, false}, {p, true}, {r, false}}, region);
+  if (x == p || x == r || p == r)
+    throw std::invalid_argument("cg_update_sum: x, p and r must be distinct quantities");
+  ExchangeEngine::ReduceScratch &sc = begin_reduction("cg_update_sum", eng, dom, !l.empty);
+  if (l.empty) return land_empty_n(sc, 2);
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  if (l.es == 4) {
+    const float al = (float)alpha; // the one rounding to the quantity's type
+    VEC_OPS_LAUNCH(float, l, cg_update_sum_kernel, stream, l.g, l.ptr[0], (const char *)l.ptr[1],
+                   (const char *)l.ptr[2], l.ptr[3], al, sc.dev);
+  } else {
+    VEC_OPS_LAUNCH(double, l, cg_update_sum_kernel, stream, l.g, l.ptr[0],
+                   (const char *)l.ptr[1], (const char *)l.ptr[2], l.ptr[3], alpha, sc.dev);
+  }
+  land_partials_n(sc, l.blocks, 2, stream);
+}
+
+double field_sum(ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
+                 int streamId) {
+  field_sum_begin(eng, dom, a, aNext, region, streamId);
+  double out[1];
+  reduction_end_n(eng, dom, out, 1);
+  return out[0];
+}
+
+std::array<double, 3> field_dot_sums(ExchangeEngine &eng, int dom, int64_t a, bool aNext,
+                                     int64_t b, bool bNext, const Rect3 &region, int streamId) {
+  field_dot_sums_begin(eng, dom, a, aNext, b, bNext, region, streamId);
+  std::array<double, 3> out{};
+  reduction_end_n(eng, dom, out.data(), 3);
+  return out;
+}
+
+std::array<double, 2> cg_update_sum(ExchangeEngine &eng, int dom, double alpha, int64_t x,
+                                    int64_t p, int64_t r, const Rect3 &region, int streamId) {
+  cg_update_sum_begin(eng, dom, alpha, x, p, r, region, streamId);
+  std::array<double, 2> out{};
+  reduction_end_n(eng, dom, out.data(), 2);
+  return out;
+}
+
+void field_axpbyc(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
+                  int64_t y, bool yNext, double c, int64_t out, bool outNext,
+                  const Rect3 &region, int streamId) {
+  const Launch l =
+      plan_launch("field_axpbyc", eng, dom, {{x, xNext}, {y, yNext}, {out, outNext}}, region);
+  if (l.empty) return;
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  if (l.es == 4) {
+    const float al = (float)alpha, be = (float)beta, cc = (float)c; // rounded once
+    VEC_OPS_LAUNCH(float, l, axpbyc_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], l.ptr[2], al, be, cc);
+  } else {
+    VEC_OPS_LAUNCH(double, l, axpbyc_kernel, stream, l.g, (const char *)l.ptr[0],
+                   (const char *)l.ptr[1], l.ptr[2], alpha, beta, c);
+  }
 }
 
 double field_dot(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,

@@ -541,6 +541,50 @@ class DistributedDomain:
         boxes = self._vector_boxes("cg_update", "all")
         return self._global_sum(self.backend.cg_update(boxes, float(alpha), qx, qp, qr))
 
+    # The sums that the projection v - mean(v) off the constant null space
+    # needs (solvers/cg.py, nullspace="constant"), each fused into a pass a
+    # CG iteration makes anyway. Every returned scalar goes through
+    # _global_sum on its own: bitwise identical on every rank.
+    def _global_sums(self, per_domain, n: int):
+        return tuple(self._global_sum([v[k] for v in per_domain]) for k in range(n))
+
+    def sum(self, a, where="all") -> float:
+        """GLOBAL sum of a(p), in fp64, deterministic like dot(); `where`
+        and the operand (a handle or Next(handle)) as in dot(). Blocks
+        until the value is there."""
+        ((qa, na),) = self._vector_operands("sum", [a])
+        boxes = self._vector_boxes("sum", where)
+        return self._global_sum(self.backend.field_sum(boxes, qa, na))
+
+    def dot_sums(self, a, b=None, where="all"):
+        """(sum a * b, sum a, sum b), GLOBAL, from ONE pass over a and b
+        (b=None: a with itself): dot()'s traffic, dot()'s determinism."""
+        (qa, na), (qb, nb) = self._vector_operands("dot_sums", [a, a if b is None else b])
+        boxes = self._vector_boxes("dot_sums", where)
+        return self._global_sums(self.backend.field_dot_sums(boxes, qa, na, qb, nb), 3)
+
+    def cg_update_sum(self, alpha: float, x, p, r):
+        """cg_update (the same arithmetic on x and r, the same sum of
+        r_new^2) returning (sum r_new^2, sum r_new), GLOBAL: the second
+        value is what projecting r off the constants needs."""
+        for h in (x, p, r):
+            if not isinstance(h, DataHandle):
+                raise TypeError("cg_update_sum: x, p and r are DataHandles")
+        (qx, _), (qp, _), (qr, _) = self._vector_operands("cg_update_sum", [x, p, r])
+        boxes = self._vector_boxes("cg_update_sum", "all")
+        return self._global_sums(
+            self.backend.cg_update_sum(boxes, float(alpha), qx, qp, qr), 2)
+
+    def axpbyc(self, alpha: float, x, beta: float, y, c: float, out, where="all"):
+        """out = alpha * x + beta * y + c, element-wise in the quantity's
+        type (alpha, beta and c are rounded to it once): axpby plus a
+        constant shift, at axpby's traffic. out may be the buffer of x or
+        of y. Enqueued on compute stream 0 like axpby."""
+        (qx, nx), (qy, ny), (qo, no) = self._vector_operands("axpbyc", [x, y, out])
+        boxes = self._vector_boxes("axpbyc", where)
+        self.backend.field_axpbyc(boxes, float(alpha), qx, nx, float(beta), qy, ny, float(c),
+                                  qo, no)
+
     # ---- geometry queries ----
     def any_methods(self, m: Method) -> bool:
         """True if any of the given transport methods are enabled

@@ -2,7 +2,10 @@
 conjugate-gradient solver (stencil_amd/solvers/cg.py) on the generic
 stencil operator. sigma > 0 is an implicit diffusion step or a screened
 Poisson problem; sigma = 0 is the Poisson problem proper, which needs a
-boundary that pins the constant (FIXED(0) or ANTIMIRROR on some axis).
+boundary that pins the constant (FIXED(0) or ANTIMIRROR on some axis) or,
+for the singular problem of a periodic box or zero-flux (MIRROR) walls,
+nullspace="constant": the solver then solves A x = b - mean(b) and returns
+the solution with mean(x) = 0 (solvers/cg.py).
 
 Four quantities x, b, r, p; only p (every iteration) and x (for a nonzero
 initial guess) are ever exchanged, each in an exchange group of its own.
@@ -45,6 +48,7 @@ class Poisson3D:
         mg: Optional[dict] = None,
         coarse_order: int = 2,
         coefficient: bool = False,
+        nullspace: Optional[str] = None,
     ):
         """A = sigma I - laplacian(order, spacing); sigma >= 0.
 
@@ -70,7 +74,17 @@ class Poisson3D:
         solver accepts are PERIODIC, FIXED(0), MIRROR and ANTIMIRROR; fold
         inhomogeneous Dirichlet data into the right-hand side. Raises
         ValueError when the problem is singular: sigma == 0 with every axis
-        periodic or MIRROR (the constant is then in A's null space)."""
+        periodic or MIRROR (the constant is then in A's null space), unless
+        nullspace="constant".
+
+        nullspace: None, or "constant" for exactly that singular problem
+        (ValueError for every other configuration: projecting a
+        non-singular problem would be wrong), with or without a
+        coefficient and with any preconditioner. ConjugateGradient then
+        projects off the constants: b may have any mean, the solution
+        comes back with mean 0. Always adds the correction quantity xc (a
+        singular A is the extreme of the nearly singular case the
+        refinement exists for)."""
         sigma = float(sigma)
         if not sigma >= 0.0:
             raise ValueError(f"Poisson3D: sigma must be >= 0, got {sigma}")
@@ -101,10 +115,19 @@ class Poisson3D:
                 kind = spec[0] if isinstance(spec, (tuple, list)) else spec
                 for f in parse_face(face):
                     kinds[FACES[f]] = Boundary(kind)
-        if sigma == 0.0 and all(
+        if nullspace not in (None, "constant"):
+            raise ValueError(f"Poisson3D: nullspace is None or 'constant', got {nullspace!r}")
+        self.nullspace = nullspace
+        singular = sigma == 0.0 and all(
             kinds.get(f, Boundary.PERIODIC) in (Boundary.PERIODIC, Boundary.MIRROR)
             for f in FACES
-        ):
+        )
+        if nullspace is not None and not singular:
+            raise ValueError(
+                "Poisson3D: nullspace='constant' is for the singular problem only: sigma == 0 "
+                "with every axis periodic or MIRROR; this one has "
+                + (f"sigma = {sigma}" if sigma != 0.0 else "a face that pins the constant"))
+        if singular and nullspace is None:
             raise ValueError(
                 "Poisson3D: sigma == 0 with every axis periodic or MIRROR is singular "
                 "(constants are in the null space); use sigma > 0 or a FIXED(0)/ANTIMIRROR face"
@@ -136,6 +159,8 @@ class Poisson3D:
             self.xc = self.dd.add_data(dt, "xc")  # CG's correction: true-residual check
             self._group_k = len(groups)
             groups.append([self.k.index])
+        elif nullspace is not None:
+            self.xc = self.dd.add_data(dt, "xc")
         self.dd.set_exchange_groups(groups)
         if boundary:
             for face, spec in boundary.items():
@@ -172,7 +197,7 @@ class Poisson3D:
             M = self.jacobi = JacobiPreconditioner(self.op)
         self.cg = ConjugateGradient(self.dd, operator, self.x, self.b, self.r, self.p,
                                     group_p=0, group_x=1, preconditioner=M, z=self.z,
-                                    correction=self.xc)
+                                    correction=self.xc, nullspace=self.nullspace)
 
     def set_coefficient(self, global_array):
         """k = the (z, y, x) global array, every value finite and > 0

@@ -814,6 +814,51 @@ class NativeBackend:
             out = [_C.reduction_end(self.engine, li) for li in range(n)]
         return out
 
+    # ---- the reductions of singular problems: several values per pass ----
+    def _reduce_n(self, boxes, n_values: int, begin) -> List[tuple]:
+        """begin(li, rect) on every local domain, then reduction_end_n on
+        each: one tuple of n_values fp64 sums per local domain"""
+        n = 0
+        try:
+            for li, (lo, hi) in enumerate(boxes):
+                begin(li, _rect3(lo, hi))
+                n += 1
+        finally:
+            out = [_C.reduction_end_n(self.engine, li, n_values) for li in range(n)]
+        return out
+
+    def field_sum(self, boxes, a: int, a_next: bool, stream_id: int = 0) -> List[float]:
+        """per local domain: sum of a over its box in fp64, deterministic;
+        the ValueErrors of field_dot"""
+        return [v[0] for v in self._reduce_n(
+            boxes, 1,
+            lambda li, rect: _C.field_sum_begin(self.engine, li, a, a_next, rect, stream_id))]
+
+    def field_dot_sums(self, boxes, a: int, a_next: bool, b: int, b_next: bool,
+                       stream_id: int = 0) -> List[tuple]:
+        """per local domain: (sum a * b, sum a, sum b) over its box from one
+        pass, in fp64, deterministic; a and b may be the same buffer"""
+        return self._reduce_n(
+            boxes, 3,
+            lambda li, rect: _C.field_dot_sums_begin(self.engine, li, a, a_next, b, b_next, rect,
+                                                     stream_id))
+
+    def cg_update_sum(self, boxes, alpha: float, x: int, p: int, r: int,
+                      stream_id: int = 0) -> List[tuple]:
+        """cg_update per local domain, returning (sum r_new^2, sum r_new)"""
+        return self._reduce_n(
+            boxes, 2,
+            lambda li, rect: _C.cg_update_sum_begin(self.engine, li, alpha, x, p, r, rect,
+                                                    stream_id))
+
+    def field_axpbyc(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
+                     y_next: bool, c: float, out: int, out_next: bool, stream_id: int = 0):
+        """out = alpha * x + beta * y + c over each local domain's box, in
+        the quantity's type; out may alias x or y. Enqueued, not awaited."""
+        for li, (lo, hi) in enumerate(boxes):
+            _C.field_axpbyc(self.engine, li, alpha, x, x_next, beta, y, y_next, c, out, out_next,
+                            _rect3(lo, hi), stream_id)
+
     def jacobi_graph_create(self, li: int, qi: int, region_lo: Vec, region_hi: Vec,
                             c_lo: Vec, c_hi: Vec) -> "_C.JacobiStepGraph":
         """whole-step replay graph (single-process single-domain path);

@@ -16,6 +16,10 @@ stream of the given ExchangeEngine; regions are global-coordinate Rect3s.
   + reduction_end split a reduction so that several local domains launch
   before any of them waits; field_scaled_update: out = alpha x + d (beta y +
   gamma z) with d a quantity
+- field_sum / field_dot_sums / cg_update_sum / field_axpbyc: the sums that
+  the projection off the constant null space needs, fused into the passes
+  of field_dot, cg_update and field_axpby; their *_begin forms end with
+  reduction_end_n
 - diffusion_apply / diffusion_inv_diagonal: the variable-coefficient
   operator sigma I - div(k grad) and omega over its diagonal
   (csrc/src/diffusion_op.hip)
@@ -27,19 +31,27 @@ from .._C import (  # noqa: F401
     StencilType,
     cg_update,
     cg_update_begin,
+    cg_update_sum,
+    cg_update_sum_begin,
     diffusion_apply,
     diffusion_inv_diagonal,
     field_axpby,
+    field_axpbyc,
     field_dot,
     field_dot_begin,
+    field_dot_sums,
+    field_dot_sums_begin,
     field_scaled_update,
     field_stats,
+    field_sum,
+    field_sum_begin,
     fill_f32,
     init_harmonic_f64,
     jacobi_step,
     mhd_div_pass,
     mhd_substep,
     reduction_end,
+    reduction_end_n,
     stencil_apply,
 )
 
@@ -50,18 +62,26 @@ __all__ = [
     "StencilType",
     "cg_update",
     "cg_update_begin",
+    "cg_update_sum",
+    "cg_update_sum_begin",
     "diffusion_apply",
     "diffusion_inv_diagonal",
     "field_axpby",
+    "field_axpbyc",
     "field_dot",
     "field_dot_begin",
+    "field_dot_sums",
+    "field_dot_sums_begin",
     "field_scaled_update",
     "field_stats",
+    "field_sum",
+    "field_sum_begin",
     "fill_f32",
     "init_harmonic_f64",
     "jacobi_step",
     "mhd_div_pass",
     "mhd_substep",
     "reduction_end",
+    "reduction_end_n",
     "stencil_apply",
 ]

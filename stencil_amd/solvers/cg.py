@@ -51,8 +51,32 @@ CLAMP and FIXED(c != 0) are refused. Inhomogeneous Dirichlet data is the
 caller's job: fold it into b (b -= A applied to the field that holds the
 boundary values in its halo and 0 inside).
 
+Singular problems. With every axis PERIODIC or MIRROR and no sigma the
+constant is in the null space of A: A x = b has a solution only for
+mean(b) = 0, and then a family x + c. `nullspace="constant"` makes the
+solver own the projection P v = v - mean(v): it solves A x = P b and
+returns the x with mean(x) = 0. A right-hand side with a mean (every
+discretised source has one) would otherwise end in a breakdown, and a
+smoother that scales per cell (the variable-coefficient multigrid) would
+feed a constant into p and x that eats mantissa. The projection adds no
+pass to the iteration; it rides on the passes the loop makes anyway:
+
+    r = b - mean(b)                      one sum, one axpbyc; bb = dot(r)
+    plain:  (rr, sr) = cg_update_sum(alpha, x, p, r)
+            rr_p = rr - sr^2 / N         = (P r) . (P r): stopping test, beta
+            p = r + beta p - sr / N      one axpbyc in the place of the axpby
+    with M: z = M r; (rz, sr, sz) = dot_sums(r, z)
+            rz_p = rz - sr sz / N        = (P r) . (P z): alpha, beta
+            p = z + beta p - sz / N      (the stopping test stays on r . r)
+    x -= mean(x)                         once, on the way out
+
+with N the global cell count. bb is the norm of P b itself, never
+b . b - (sum b)^2 / N, which cancels. The correction loop checks
+P (b - A x) and projects x after the last x += d. GeometricMultigrid runs
+on such operators as it is (see its module docstring).
+
 Every scalar the iteration branches on comes from `dd.dot` /
-`dd.cg_update`, which return the bitwise identical value on every rank, so
+`dd.cg_update` and their *_sum(s) forms, which return the bitwise identical value on every rank, so
 all ranks stop in the same iteration for the same reason.
 """
 from __future__ import annotations
@@ -131,11 +155,43 @@ def check_boundary(who: str, dd: DistributedDomain, handles):
                     )
 
 
+def check_constant_nullspace(who: str, dd: DistributedDomain, operator, handles):
+    """ValueError unless the constant is in the null space of A: every face
+    of the given quantities PERIODIC or MIRROR, and an operator without a
+    zeroth-order term"""
+    spec = dd.boundary
+    if spec is not None:
+        for h in handles:
+            for a in range(3):
+                if spec.periodic[a]:
+                    continue
+                for s in (0, 1):
+                    k = spec.kind(h.index, a, s)
+                    if k != Boundary.MIRROR:
+                        raise ValueError(
+                            f"{who}: nullspace='constant' but boundary {k.name} on face "
+                            f"{_FACES[2 * a + s]} of quantity {h.name or h.index} pins the "
+                            "constant: A is not singular (every face must be PERIODIC or MIRROR)"
+                        )
+    if isinstance(operator, Stencil):
+        total = math.fsum(operator.weights)
+        scale = math.fsum(abs(w) for w in operator.weights)
+        if not abs(total) <= 64.0 * float(np.finfo(np.float64).eps) * scale:
+            raise ValueError(
+                f"{who}: nullspace='constant' but the stencil's weights sum to {total!r}, "
+                "not 0: the constant is not in the null space of A")
+    elif float(operator.sigma) != 0.0:
+        raise ValueError(
+            f"{who}: nullspace='constant' but the DiffusionOperator has sigma = "
+            f"{operator.sigma!r} != 0: A is not singular")
+
+
 class ConjugateGradient:
     def __init__(self, dd: DistributedDomain, operator, x: DataHandle, b: DataHandle,
                  r: DataHandle, p: DataHandle, group_p: int = 0,
                  group_x: Optional[int] = None, preconditioner=None,
-                 z: Optional[DataHandle] = None, correction: Optional[DataHandle] = None):
+                 z: Optional[DataHandle] = None, correction: Optional[DataHandle] = None,
+                 nullspace: Optional[str] = None):
         """dd is realized and holds x, b, r and p, four distinct quantities
         of one float type. operator is a Stencil or a DiffusionOperator of
         dd (of the same float type). group_p is the exchange group that
@@ -153,7 +209,18 @@ class ConjugateGradient:
         correction: None, or one more distinct quantity of the same type.
         solve() then verifies the TRUE residual b - A x once the recursive
         one has converged, and refines until it meets the tolerance too
-        (see solve()). Needs group_x."""
+        (see solve()). Needs group_x.
+
+        nullspace: None, or "constant" for a singular A whose null space is
+        the constants: solve() then solves A x = P b, P v = v - mean(v),
+        and returns the solution with mean(x) = 0 (module docstring).
+        ValueError unless A is such an operator: every face of p and x
+        PERIODIC or MIRROR, a DiffusionOperator with sigma == 0, a Stencil
+        whose weights sum to zero (to 64 eps of their absolute sum: the
+        Laplacian factories round their weights)."""
+        if nullspace not in (None, "constant"):
+            raise ValueError(
+                f"ConjugateGradient: nullspace is None or 'constant', got {nullspace!r}")
         if not dd._realized:
             raise ValueError("ConjugateGradient: construct after dd.realize()")
         hs = (x, b, r, p)
@@ -193,6 +260,11 @@ class ConjugateGradient:
         if group_x is not None and not (0 <= group_x < len(groups) and x.index in groups[group_x]):
             raise ValueError(f"ConjugateGradient: x is not in exchange group {group_x}")
         check_boundary("ConjugateGradient", dd, (p, x))
+        if nullspace is not None:
+            check_constant_nullspace("ConjugateGradient", dd, operator, (p, x))
+        self.nullspace = nullspace
+        self._cells = float(dd.size[0]) * float(dd.size[1]) * float(dd.size[2])  # N
+        self._bb = 0.0  # ||P b||^2 of the last nullspace solve, for _refine
         self.dd, self.A = dd, operator
         self.x, self.b, self.r, self.p = x, b, r, p
         self.group_p, self.group_x = group_p, group_x
@@ -201,6 +273,7 @@ class ConjugateGradient:
         # update = cg_update + the p update
         self.phase_times = {"operator": 0.0, "dot": 0.0, "update": 0.0}
         self.M, self.z, self.correction = preconditioner, z, correction
+        self.corrections = 0  # correction solves of the last solve()
         if preconditioner is not None:
             self.phase_times["precond"] = 0.0  # z = M r and r . z
 
@@ -242,20 +315,45 @@ class ConjugateGradient:
         count and are limited by max_iter like the others. A true residual
         that a correction does not bring below 0.9 x the previous one ends
         the solve with converged=False, reason="stagnated": the tolerance
-        is then below what the type can resolve."""
-        res = self._solve(tol, max_iter, x0_zero, overlap)
-        if self.correction is None or not res.converged or res.reason == "zero_rhs":
+        is then below what the type can resolve.
+
+        With nullspace="constant" everything above holds with P b in the
+        place of b and P (b - A x) in the place of the true residual:
+        `residuals` and the stopping test are relative to ||P b||, a
+        constant b gives "zero_rhs", b is never written, and x is
+        projected (x -= mean(x)) on every exit that returns a solution."""
+        self.corrections = 0
+        if self.nullspace is None:
+            res = self._solve(tol, max_iter, x0_zero, overlap)
+            if self.correction is None or not res.converged or res.reason == "zero_rhs":
+                return res
+            return self._refine(res, tol, max_iter, overlap)
+        res = self._solve_projected(tol, max_iter, x0_zero, overlap)
+        if res.reason == "zero_rhs":
             return res
-        return self._refine(res, tol, max_iter, overlap)
+        if self.correction is not None and res.converged:
+            res = self._refine(res, tol, max_iter, overlap)
+        self._project(self.x)
+        return res
+
+    def _project(self, h: DataHandle):
+        """h -= mean(h): one sum and one axpbyc"""
+        dd = self.dd
+        s = dd.sum(h)
+        dd.axpbyc(1.0, h, 0.0, h, -s / self._cells, out=h)
+        dd.backend.sync_compute()
 
     def _refine(self, res: CGResult, tol, max_iter, overlap) -> CGResult:
         dd, x, b, r, p, d = self.dd, self.x, self.b, self.r, self.p, self.correction
-        bb = dd.dot(b)
+        ns = self.nullspace is not None
+        bb = self._bb if ns else dd.dot(b)
         limit = tol * tol * bb
         residuals, its, prev = list(res.residuals), res.iterations, None
         while True:
             self._apply(x, self.group_x, overlap)
             dd.axpby(1.0, b, -1.0, Next(x), out=r)
+            if ns:  # the true residual is P (b - A x); b carries its mean
+                self._project(r)
             rr = dd.dot(r)
             if not math.isfinite(rr):
                 return CGResult(False, its, residuals[:-1] + [float("nan")], "breakdown")
@@ -267,16 +365,23 @@ class ConjugateGradient:
             if its >= max_iter:
                 return CGResult(False, its, residuals, "max_iter")
             prev = rr
+            self.corrections += 1
             dd.axpby(0.0, r, 0.0, r, out=d)
             dd.axpby(1.0, r, 0.0, r, out=p)
             dd.backend.sync_compute()
             self.x = d  # the loops below update self.x
             try:
-                if self.M is not None:
-                    inner = self._iterate_preconditioned(limit, bb, residuals, max_iter - its,
-                                                         overlap)
+                left = max_iter - its
+                if ns and self.M is not None:
+                    inner = self._iterate_preconditioned_projected(limit, bb, residuals, left,
+                                                                   overlap)
+                elif ns:
+                    inner = self._iterate_plain_projected(rr, limit, bb, residuals, left,
+                                                          overlap)
+                elif self.M is not None:
+                    inner = self._iterate_preconditioned(limit, bb, residuals, left, overlap)
                 else:
-                    inner = self._iterate_plain(rr, limit, bb, residuals, max_iter - its, overlap)
+                    inner = self._iterate_plain(rr, limit, bb, residuals, left, overlap)
             finally:
                 self.x = x
             dd.axpby(1.0, x, 1.0, d, out=x)
@@ -386,6 +491,126 @@ class ConjugateGradient:
                 return CGResult(False, it, residuals, "breakdown")
             t3 = time.perf_counter()
             dd.axpby(1.0, z, rz_new / rz, p, out=p)
+            dd.backend.sync_compute()  # before the next exchange reads p
+            rz = rz_new
+            self.phase_times["update"] += time.perf_counter() - t3
+        return CGResult(False, max_iter, residuals, "max_iter")
+
+    # ---- nullspace="constant": the loops above with P v = v - mean(v) ----
+    def _solve_projected(self, tol, max_iter, x0_zero, overlap) -> CGResult:
+        """_solve for A x = P b. r = P b first, and bb = r . r of that r:
+        the norm every residual is relative to."""
+        dd, x, b, r, p = self.dd, self.x, self.b, self.r, self.p
+        self.phase_times = {k: 0.0 for k in self.phase_times}
+        if not x0_zero and self.group_x is None:
+            raise ValueError("solve(x0_zero=False) needs group_x, the exchange group of x")
+        sb = dd.sum(b)
+        if not math.isfinite(sb):
+            return CGResult(False, 0, [float("nan")], "breakdown")
+        dd.axpbyc(1.0, b, 0.0, b, -sb / self._cells, out=r)
+        bb = dd.dot(r)
+        if not math.isfinite(bb):
+            return CGResult(False, 0, [float("nan")], "breakdown")
+        self._bb = bb
+        if bb == 0.0:
+            dd.axpby(0.0, r, 0.0, r, out=x)  # P b is all zeros: so is x
+            dd.backend.sync_compute()
+            return CGResult(True, 0, [0.0], "zero_rhs")
+        if x0_zero:
+            dd.axpby(0.0, r, 0.0, r, out=x)
+            rr = bb
+        else:
+            self._apply(x, self.group_x, overlap)
+            dd.axpby(1.0, r, -1.0, Next(x), out=r)
+            self._project(r)
+            rr = dd.dot(r)
+        dd.axpby(1.0, r, 0.0, r, out=p)
+        dd.backend.sync_compute()  # the exchange reads p on other streams
+        residuals = [math.sqrt(rr / bb)] if math.isfinite(rr) else [float("nan")]
+        if not math.isfinite(rr):
+            return CGResult(False, 0, residuals, "breakdown")
+        limit = tol * tol * bb
+        if rr <= limit:
+            return CGResult(True, 0, residuals, "converged")
+        if self.M is not None:
+            return self._iterate_preconditioned_projected(limit, bb, residuals, max_iter, overlap)
+        return self._iterate_plain_projected(rr, limit, bb, residuals, max_iter, overlap)
+
+    def _iterate_plain_projected(self, rr, limit, bb, residuals, max_iter, overlap) -> CGResult:
+        """_iterate_plain from a mean-free p = r. cg_update_sum returns
+        sum r next to r . r: rr_p = (P r) . (P r) drives the stopping test
+        and beta, and p = P r + beta p is one axpbyc. No pass more than
+        the plain loop."""
+        dd, x, r, p, n = self.dd, self.x, self.r, self.p, self._cells
+        for it in range(1, max_iter + 1):
+            t0 = time.perf_counter()
+            self._apply(p, self.group_p, overlap)
+            t1 = time.perf_counter()
+            pap = dd.dot(p, Next(p))
+            t2 = time.perf_counter()
+            self.phase_times["operator"] += t1 - t0
+            self.phase_times["dot"] += t2 - t1
+            if not (math.isfinite(pap) and pap > 0.0):
+                return CGResult(False, it - 1, residuals, "breakdown")
+            alpha = rr / pap
+            rr_raw, sr = dd.cg_update_sum(alpha, x, p, r)
+            rr_new = max(rr_raw - sr * sr / n, 0.0)
+            if not math.isfinite(rr_new):
+                self.phase_times["update"] += time.perf_counter() - t2
+                return CGResult(False, it, residuals + [float("nan")], "breakdown")
+            residuals.append(math.sqrt(rr_new / bb))
+            if rr_new <= limit:
+                self.phase_times["update"] += time.perf_counter() - t2
+                return CGResult(True, it, residuals, "converged")
+            dd.axpbyc(1.0, r, rr_new / rr, p, -sr / n, out=p)
+            dd.backend.sync_compute()  # before the next exchange reads p
+            rr = rr_new
+            self.phase_times["update"] += time.perf_counter() - t2
+        return CGResult(False, max_iter, residuals, "max_iter")
+
+    def _precondition_projected(self):
+        """z = M r; returns ((P r) . (P z), sum z) from one dot_sums pass"""
+        t0 = time.perf_counter()
+        self.M.apply(self.r, self.z)
+        rz, sr, sz = self.dd.dot_sums(self.r, self.z)
+        self.phase_times["precond"] += time.perf_counter() - t0
+        return rz - sr * sz / self._cells, sz
+
+    def _iterate_preconditioned_projected(self, limit, bb, residuals, max_iter,
+                                          overlap) -> CGResult:
+        """_iterate_preconditioned with P z in the place of z: M r has a
+        constant component even for a mean-free r (a smoother that scales
+        per cell), which must reach neither p nor x. The stopping test
+        stays on cg_update's r . r; the breakdown rules apply to the
+        projected r . z."""
+        dd, x, r, p, z, n = self.dd, self.x, self.r, self.p, self.z, self._cells
+        rz, sz = self._precondition_projected()
+        if not (math.isfinite(rz) and rz > 0.0):
+            return CGResult(False, 0, residuals, "breakdown")
+        dd.axpbyc(1.0, z, 0.0, z, -sz / n, out=p)
+        dd.backend.sync_compute()
+        for it in range(1, max_iter + 1):
+            t0 = time.perf_counter()
+            self._apply(p, self.group_p, overlap)
+            t1 = time.perf_counter()
+            pap = dd.dot(p, Next(p))
+            t2 = time.perf_counter()
+            self.phase_times["operator"] += t1 - t0
+            self.phase_times["dot"] += t2 - t1
+            if not (math.isfinite(pap) and pap > 0.0):
+                return CGResult(False, it - 1, residuals, "breakdown")
+            rr_new = dd.cg_update(rz / pap, x, p, r)
+            self.phase_times["update"] += time.perf_counter() - t2
+            if not math.isfinite(rr_new):
+                return CGResult(False, it, residuals + [float("nan")], "breakdown")
+            residuals.append(math.sqrt(rr_new / bb))
+            if rr_new <= limit:
+                return CGResult(True, it, residuals, "converged")
+            rz_new, sz = self._precondition_projected()
+            if not (math.isfinite(rz_new) and rz_new > 0.0):
+                return CGResult(False, it, residuals, "breakdown")
+            t3 = time.perf_counter()
+            dd.axpbyc(1.0, z, rz_new / rz, p, -sz / n, out=p)
             dd.backend.sync_compute()  # before the next exchange reads p
             rz = rz_new
             self.phase_times["update"] += time.perf_counter() - t3

@@ -35,6 +35,17 @@ first sweep e = d f. Level 0 uses the operator's dinv quantity for d.
 refresh_coefficients() redoes restriction, exchanges and diagonals after k
 changed. The constant-coefficient path is the one above, unchanged.
 
+Singular operators. With every face PERIODIC or MIRROR and sigma = 0 every
+level's A has the constants in its null space, and the cycle runs on it as
+it is: it is a fixed number of damped Jacobi sweeps, nothing is inverted,
+and the coarsest level is swept like the others. Restriction by the mean
+of 8 keeps a mean-free residual mean-free on every level. What the cycle
+does not keep is the mean of its output: z = M r has a constant component
+that the operator cannot see, small for a constant coefficient, of the
+order of z itself when d = omega / diag varies per cell. Removing it is the
+caller's job; ConjugateGradient(nullspace="constant") does it inside the
+r . z pass (solvers/cg.py) and needs nothing from this class.
+
 Not there: a whole-cycle hipGraph (each level costs host launches and
 syncs, see phase_times), agglomeration of coarse levels onto fewer GPUs,
 trilinear transfer, Galerkin coarse operators, harmonic-mean or

@@ -579,5 +579,52 @@ class TorchBackend:
         self.field_axpby(boxes, 1.0, r, False, -alpha, p, True, r, False)
         return self.field_dot(boxes, r, False, r, False)
 
+    # ---- the reductions of singular problems (vector_ops.hip's second family) ----
+    def field_sum(self, boxes, a, a_next, stream_id=0):
+        """per local domain: sum of a over its box, in fp64"""
+        out = []
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_sum", li, lo, hi, [(a, a_next)])
+            out.append(0.0 if v is None else float(v[0].double().sum()))
+        return out
+
+    def field_dot_sums(self, boxes, a, a_next, b, b_next, stream_id=0):
+        """per local domain: (sum a * b, sum a, sum b) over its box, products
+        and sums in fp64"""
+        out = []
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_dot_sums", li, lo, hi, [(a, a_next), (b, b_next)])
+            if v is None:
+                out.append((0.0, 0.0, 0.0))
+                continue
+            ta, tb = v[0].double(), v[1].double()
+            out.append((float((ta * tb).sum()), float(ta.sum()), float(tb.sum())))
+        return out
+
+    def cg_update_sum(self, boxes, alpha, x, p, r, stream_id=0):
+        """cg_update, returning (dot(r, r), sum r) per domain"""
+        if x == p or x == r or p == r:
+            raise ValueError("cg_update_sum: x, p and r must be distinct quantities")
+        for li, (lo, hi) in enumerate(boxes):  # validate every operand before any write
+            self._vector_views("cg_update_sum", li, lo, hi,
+                               [(x, False), (p, False), (p, True), (r, False)])
+        self.field_axpby(boxes, 1.0, x, False, alpha, p, False, x, False)
+        self.field_axpby(boxes, 1.0, r, False, -alpha, p, True, r, False)
+        return [(rr, sr) for rr, sr, _ in self.field_dot_sums(boxes, r, False, r, False)]
+
+    def field_axpbyc(self, boxes, alpha, x, x_next, beta, y, y_next, c, out, out_next,
+                     stream_id=0):
+        """out = alpha * x + beta * y + c in the quantity's type, alpha, beta
+        and c rounded to it once; summed left to right, no FMA"""
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_axpbyc", li, lo, hi,
+                                   [(x, x_next), (y, y_next), (out, out_next)])
+            if v is None:
+                continue
+            tx, ty, tout = v
+            al, be, cc = (torch.tensor(s, dtype=tx.dtype, device=tx.device)
+                          for s in (alpha, beta, c))
+            tout.copy_(al * tx + be * ty + cc)
+
     def sync_compute(self):
         pass
