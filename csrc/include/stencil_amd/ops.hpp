@@ -45,6 +45,11 @@ void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, flo
 // buffer (no translate, no in-graph swap; STENCIL_JAC_WRAP=0 turns it
 // off). Halos are then stale after a step until the next exchange.
 // is_wrap() tells which of the two the graph is.
+// A wrap graph also captures the fused two-step kernel (STENCIL_JAC_FUSE2=0
+// turns that off; is_fused2() tells): launch(n) then replays n/2 fused
+// graphs and, for odd n, one single step. Every replay, fused or single, is
+// one buffer swap, so after a fused pair the result sits in the buffer that
+// was `next` and the new `next` holds time t, not t+1.
 // Ownership (all four graph classes below): the creator returns the only
 // owner; destroying it waits for its stream and frees its streams, events
 // and graph execs. A graph must be destroyed before the engine and domains
@@ -53,6 +58,8 @@ class JacobiStepGraph final : public ReplayGraph {
 public:
   void launch(int64_t nSteps);
   bool is_wrap() const { return wrap_; }
+  // whether launch(n >= 2) replays fused two-step graphs (see below)
+  bool is_fused2() const { return fused2_; }
 
 private:
   friend std::unique_ptr<JacobiStepGraph> jacobi_graph_create(ExchangeEngine &, int, int64_t,
@@ -63,10 +70,17 @@ private:
   // wrap graph: the stencil kernel alone; the device tables are flipped
   // by launch(), not by a graph node
   bool wrap_ = false;
+  // fused pairs: one more graph per parity, each the two-step kernel alone
+  hipGraphExec_t exec2_[2] = {nullptr, nullptr};
+  bool fused2_ = false;
 };
 std::unique_ptr<JacobiStepGraph> jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi,
                                                      const Rect3 &region,
                                                      const Rect3 &computeRegion);
+
+// Test hook: out[i] = div6(in[i]) (device_util.hpp), computed on the current
+// device from host arrays of n floats; blocks until done.
+void div6_f32(const float *in, float *out, int64_t n);
 
 // Multi-rank whole-step graphs (see csrc/src/jacobi.hip): per parity,
 // A = [interior + translates + staged packs], B = [staged unpacks +

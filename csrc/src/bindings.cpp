@@ -3,6 +3,7 @@
 // The native library is self-contained C++/HIP (no libtorch dependency);
 // staging buffers are exported to Python through DLPack capsules so
 // torch.from_dlpack can alias them for RCCL (torch.distributed) transport.
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -613,6 +614,17 @@ PYBIND11_MODULE(_C, m) {
       py::arg("handle"), py::arg("n_steps") = 1);
   m.def("jacobi_graph_sync", [](JacobiStepGraph &g) { g.sync(); });
   m.def("jacobi_graph_is_wrap", [](JacobiStepGraph &g) { return g.is_wrap(); });
+  m.def("jacobi_graph_is_fused2", [](JacobiStepGraph &g) { return g.is_fused2(); });
+  // test only: the device division helper (device_util.hpp div6) applied to
+  // every element of a float32 array, on the current device
+  m.def(
+      "div6_f32",
+      [](py::array_t<float, py::array::c_style | py::array::forcecast> x) {
+        py::array_t<float> out(x.size());
+        div6_f32(x.data(), out.mutable_data(), (int64_t)x.size());
+        return out;
+      },
+      py::arg("x"));
   m.def(
       "jacobi_mr_graph_create",
       [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,

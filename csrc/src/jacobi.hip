@@ -24,6 +24,18 @@
 //     alternating runs (profiles/README.md). Halos are stale after steps
 //     on this path until the next exchange(). STENCIL_JAC_WRAP=0 restores
 //     the translate graph.
+//   - the same runs, two steps at a time: run(n >= 2) replays
+//     jacobi_kernel_fuse2, which reads time t and writes time t+2 with the
+//     t+1 values held in LDS and registers only, so the field crosses HBM
+//     once per two steps (the single-step kernel already streams within a
+//     few percent of its copy roofline; the round trip between two steps
+//     was the traffic left to remove). An odd n ends with one single step,
+//     step() stays the single-step kernel. Its division is the 3-instruction
+//     div6 of device_util.hpp, bit for bit the IEEE quotient; the
+//     single-step kernels keep `/ 6.0f` (no measurable difference there:
+//     they wait on memory at 8 waves/SIMD). 0.531 vs 0.722 ms/step, median
+//     of 5 alternating runs (profiles/README.md). STENCIL_JAC_FUSE2=0 forces
+//     single-step replays.
 // Hot/cold sphere sources match the reference's behavior (truncated-int
 // sqrtf distance, HOT=1/COLD=0 fixed cells) so results are comparable.
 #include <hip/hip_runtime.h>
@@ -400,6 +412,258 @@ jacobi_kernel_v4_lds(std::conditional_t<WRAP, JacobiWrapParams, JacobiParams> p)
   }
 }
 
+__device__ __forceinline__ int32_t pmod(int32_t a, int32_t n) {
+  const int32_t m = a % n;
+  return m < 0 ? m + n : m;
+}
+
+// Two time steps in one pass over memory, for the same launch the WRAP
+// kernel above serves (whole domain, periodic on every axis, vecAll row
+// extension): reads `src` at time t, writes time t+2 into `dst`; the t+1
+// values exist only in LDS and registers, so the field makes one trip
+// through HBM per TWO steps.
+//
+// Tiling: a 64 x NY block marches z. Lane (tx, ry) owns the float4 at
+// vector blockIdx.x*64+tx of row blockIdx.y*(NY-2)-1+ry. Every lane
+// computes stage 1 (time t+1) of its vector, the inner NY-2 rows also
+// compute stage 2 (time t+2) and store it: 2 of NY rows are redundant
+// stage-1 work (25% at NY = 8), and there is NO x halo lane.
+//   y: stage 1 reads the t rows above and below from tT (NY+2 rows: the
+//      block's own, plus one halo row staged by ry==0 and one by ry==NY-1),
+//      stage 2 reads the t+1 rows above and below from tS (NY rows). Both
+//      are ping-pong pairs, one barrier per plane: a plane's reads all
+//      precede the barrier after which the other half is overwritten.
+//   z: the t planes z-1, z, z+1 and the t+1 planes z-2, z-1, z roll in
+//      registers; iteration z computes stage 1 of plane z and stage 2 of
+//      plane z-1. A block owns a chunk of planes [lz0, zEnd) and runs the
+//      loop over lz0-1 .. zEnd: 2 extra stage-1 planes and 4 extra t planes
+//      per chunk. Vector loads (own vector and halo row) run two planes
+//      ahead of their use, scalar loads one (see the loop).
+//   x: inside a vector the neighbours are components; across vectors stage
+//      1 loads the two t scalars from global memory as the WRAP kernel does
+//      and stage 2 reads the t+1 scalar from the neighbouring lane's tS
+//      entry. At a tile's two x edges that neighbour belongs to another
+//      block (or, at a row's end, is the periodic image of the row's other
+//      end), so lanes 0 and 1 of each wave (= row) compute that single t+1
+//      cell themselves, from six t scalars, and hand it to the edge lanes:
+//      one two-lane divergent section per wave and plane, instead of two
+//      halo lanes per row that would push 188 vectors into a fourth,
+//      nearly empty block column.
+// Periodic wrap is a true modulo on every axis (rows and planes by index,
+// x by the row's true first/last cell), so extents down to x=8, y=1, z=1
+// are exact; the sphere override runs after each stage at the WRAPPED
+// global coordinate of the cell it produced. Overshoot components of a
+// row's first/last vector hold garbage at both stages and are stored, like
+// the WRAP kernel's, only into cells row_extension mode 1 permits; no true
+// cell ever reads one (the wl*/wr* selects replace exactly those
+// neighbours). No halo cell is read. No lane returns before a barrier:
+// out-of-range lanes clamp or wrap their coordinates and skip the store.
+// The division is div6 (device_util.hpp): 3 instructions per value instead
+// of the IEEE expansion's 11, the same bits.
+// gfx950 resource usage (-Rpass-analysis=kernel-resource-usage), NY = 8:
+//   122 VGPRs, 82 SGPRs, 0 scratch, 4 waves/SIMD, 36864 B LDS: two blocks
+//   (16 waves) per CU, bound by the VGPRs.
+// Measured at 750^3 (profiles/README.md, "Fused two-step jacobi graph").
+template <int NY>
+__global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams p) {
+  __shared__ float4 tT[2][NY + 2][64];
+  __shared__ float4 tS[2][NY][64];
+  const int32_t tx = threadIdx.x;
+  const int32_t ry = threadIdx.y;
+  const int32_t body4 = p.extX / 4; // vecAll: extX % 4 == 0
+  const int32_t ub = blockIdx.x * 64;
+  const int32_t u0 = ub + tx;
+  const int32_t u = min(u0, body4 - 1);
+  // rows: unwrapped yb, and the wrapped rows the lane touches
+  const int32_t yb = (int32_t)blockIdx.y * (NY - 2) - 1 + ry;
+  const int32_t yo = pmod(yb, p.extY), ym = pmod(yb - 1, p.extY), yp = pmod(yb + 1, p.extY);
+  const bool valid = u0 < body4 && ry >= 1 && ry <= NY - 2 && yb < p.extY;
+  // planes: the chunk is derived from the grid, so the launcher alone
+  // decides its length
+  const int32_t zc = (p.extZ + (int32_t)gridDim.z - 1) / (int32_t)gridDim.z;
+  const int32_t lz0 = blockIdx.z * zc;
+  const int32_t zEnd = min(lz0 + zc, p.extZ);
+
+  // cell (extended index 0, row 0, plane 0) of both buffers
+  const int64_t a0 = p.loX - p.allocX;
+  const int64_t org = (p.loZ - p.allocZ) * p.plane + (p.loY - p.allocY) * p.pitch + a0 * 4;
+  const char *rowO = p.src + org + (int64_t)yo * p.pitch; // own row, plane 0
+  const char *rowM = p.src + org + (int64_t)ym * p.pitch;
+  const char *rowP = p.src + org + (int64_t)yp * p.pitch;
+  const char *cell = rowO + (int64_t)u * 16;
+  // the halo row this lane stages into tT (ry == 0: below, ry == NY-1: above)
+  const char *hcell = (ry == 0 ? rowM : rowP) + (int64_t)u * 16;
+  const bool stagesHalo = ry == 0 || ry == NY - 1;
+  const int32_t hrow = ry == 0 ? 0 : NY + 1;
+  char *dcell = p.dst + org + (int64_t)yo * p.pitch + (int64_t)u * 16;
+  const int32_t gx = (int32_t)p.loX + u * 4;
+  const int32_t gy = (int32_t)p.loY + yo;
+
+  const int32_t cw = (int32_t)(p.cHiX - p.cLoX);
+  const int32_t hotX = (int32_t)p.cLoX + cw / 3, coldX = (int32_t)p.cLoX + cw * 2 / 3;
+  const int32_t cY = (int32_t)(p.cLoY + p.cHiY) / 2, cZ = (int32_t)(p.cLoZ + p.cHiZ) / 2;
+  const int32_t srad = cw / 10;
+  auto sphere4 = [&](int32_t gzz, float4 &out) {
+    const int32_t dy = gy - cY, dz = gzz - cZ;
+    const int32_t yz2 = dy * dy + dz * dz;
+    if (yz2 >= (srad + 1) * (srad + 1)) return;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int32_t dxh = gx + i - hotX, dxc = gx + i - coldX;
+      if ((int32_t)__fsqrt_rn((float)(dxh * dxh + yz2)) <= srad)
+        (&out.x)[i] = 1.0f;
+      else if ((int32_t)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad)
+        (&out.x)[i] = 0.0f;
+    }
+  };
+
+  // x wrap of the row's true end cells, as in the WRAP kernel: extended
+  // index `under` is the first true cell, `last` the last one
+  const int32_t under = (int32_t)(p.trueLoX - p.loX); // 0..3
+  const int32_t last = under + p.trueExtX - 1;        // in vector body4-1
+  const int32_t lastC = last & 3;                     // 3 - over
+  const bool first = u == 0, lastLane = u == body4 - 1;
+  const int32_t leftOff = first ? last * 4 : -4;
+  const int32_t rightOff = lastLane ? (under - 4 * u) * 4 : 16;
+  const bool wl1 = first && under == 1, wl2 = first && under == 2, wl3 = first && under == 3;
+  const bool wr0 = lastLane && lastC == 0, wr1 = lastLane && lastC == 1,
+             wr2 = lastLane && lastC == 2;
+  // one stencil evaluation of a vector: c its own plane (x neighbours
+  // inside), l / r the scalars across its ends, then +y -y +z -z
+  auto stencil4 = [&](const float4 &c, float l, float r, const float4 &py, const float4 &my,
+                      const float4 &pz, const float4 &mz) {
+    float4 s;
+    s.x = ((wr0 ? r : c.y) + l + py.x + my.x + pz.x + mz.x);
+    s.y = ((wr1 ? r : c.z) + (wl1 ? l : c.x) + py.y + my.y + pz.y + mz.y);
+    s.z = ((wr2 ? r : c.w) + (wl2 ? l : c.y) + py.z + my.z + pz.z + mz.z);
+    s.w = (r + (wl3 ? l : c.z) + py.w + my.w + pz.w + mz.w);
+    return div6(s);
+  };
+
+  // tile x edges (uniform per block): rl is the last lane that holds a
+  // vector of its own; eL / eR are the extended indices of the true cells
+  // just outside the tile, wrapped at the row's ends. Lane 0 computes the
+  // t+1 value of eL, lane 1 that of eR.
+  const int32_t rl = min(63, body4 - 1 - ub);
+  const int32_t eL = ub == 0 ? last : ub * 4 - 1;
+  const int32_t eR = ub + 63 >= body4 - 1 ? under : (ub + 64) * 4;
+  const int32_t eE = tx == 0 ? eL : eR;
+  const int32_t eXm = (eE == under ? last : eE - 1) * 4;
+  const int32_t eXp = (eE == last ? under : eE + 1) * 4;
+  const int32_t gxE = (int32_t)p.loX + eE;
+
+  // wrapped plane indices of the rolling window: i0 is the plane stage 1
+  // produces this iteration, iP3 the plane requested in it
+  int32_t iM1 = pmod(lz0 - 2, p.extZ), i0 = pmod(lz0 - 1, p.extZ);
+  int32_t iP1 = pmod(lz0, p.extZ), iP2 = pmod(lz0 + 1, p.extZ), iP3 = pmod(lz0 + 2, p.extZ);
+  auto zoff = [&](int32_t i) { return (int64_t)i * p.plane; };
+
+  // Vector loads run TWO planes ahead of their use (one plane per wave in
+  // flight cannot cover HBM latency at 4 waves/SIMD): plane zz+1 and zz+2
+  // sit in the slot pairs (vA, hA) / (vB, hB), which alternate per iteration.
+  // The loop is unrolled by two so that a slot is a fixed register set that
+  // a load writes directly; copying an in-flight slot would wait for it.
+  // (The compiler still copies the slots at the loop latch and drains the
+  // load queue there once per two planes. A variant without that drain,
+  // every wait in the loop partial, measured the same step time, 0.532 vs
+  // 0.532 ms in alternating runs: not kept.)
+  float4 cm = *(const float4 *)(cell + zoff(iM1));
+  float4 cc = *(const float4 *)(cell + zoff(i0));
+  float l = *(const float *)(cell + zoff(i0) + leftOff);
+  float r = *(const float *)(cell + zoff(i0) + rightOff);
+  tT[0][ry + 1][tx] = cc;
+  if (stagesHalo) tT[0][hrow][tx] = *(const float4 *)(hcell + zoff(i0));
+  float4 vA = *(const float4 *)(cell + zoff(iP1)), hA = *(const float4 *)(hcell + zoff(iP1));
+  float4 vB = *(const float4 *)(cell + zoff(iP2)), hB = *(const float4 *)(hcell + zoff(iP2));
+  float4 sm = make_float4(0.f, 0.f, 0.f, 0.f), sc = sm;
+  float qxp = 0.f, qxm = 0.f, qyp = 0.f, qym = 0.f, qzp = 0.f, qzm = 0.f;
+  __syncthreads();
+  int tb = 0, sb = 0;
+  // one plane: v / h hold plane zz+1 on entry and are re-requested with
+  // plane zz+3
+  auto iteration = [&](int32_t zz, float4 &v, float4 &h) {
+    const float4 cp = v, hp = h;
+    // Requests, every lane and wave alike (a wait counts loads in issue
+    // order, and only straight-line code lets the compiler count exactly).
+    // First what the NEXT iteration needs, all of it in planes already
+    // requested: the x scalars of plane zz+1 and, for lanes 0 / 1, the six
+    // t neighbours of their edge cell in plane zz (the other lanes load the
+    // same addresses as lane 1 and drop them).
+    const float ln = *(const float *)(cell + zoff(iP1) + leftOff);
+    const float rn = *(const float *)(cell + zoff(iP1) + rightOff);
+    const float nxp = *(const float *)(rowO + zoff(i0) + eXp);
+    const float nxm = *(const float *)(rowO + zoff(i0) + eXm);
+    const float nyp = *(const float *)(rowP + zoff(i0) + eE * 4);
+    const float nym = *(const float *)(rowM + zoff(i0) + eE * 4);
+    const float nzp = *(const float *)(rowO + zoff(iP1) + eE * 4);
+    const float nzm = *(const float *)(rowO + zoff(iM1) + eE * 4);
+    // then plane zz+3, last: a wait for the scalars above leaves it in flight
+    // (waves that stage no halo row re-read their own vector)
+    v = *(const float4 *)(cell + zoff(iP3));
+    h = *(const float4 *)(hcell + zoff(iP3));
+
+    // stage 1: time t+1 of plane zz
+    float4 s = stencil4(cc, l, r, tT[tb][ry + 2][tx], tT[tb][ry][tx], cp, cm);
+    sphere4((int32_t)p.loZ + i0, s);
+
+    // stage 2: time t+2 of plane zz-1, from the t+1 planes zz-2 (sm),
+    // zz-1 (sc, tS[sb^1]) and zz (s)
+    if (zz > lz0) {
+      float e1 = 0.f;
+      if (tx < 2) {
+        e1 = div6(qxp + qxm + qyp + qym + qzp + qzm);
+        const int32_t dy = gy - cY, dz = (int32_t)p.loZ + iM1 - cZ;
+        const int32_t yz2 = dy * dy + dz * dz;
+        const int32_t dxh = gxE - hotX, dxc = gxE - coldX;
+        if ((int32_t)__fsqrt_rn((float)(dxh * dxh + yz2)) <= srad)
+          e1 = 1.0f;
+        else if ((int32_t)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad)
+          e1 = 0.0f;
+      }
+      const float eRight = __shfl(e1, 1);
+      const float l2 = tx == 0 ? e1 : tS[sb ^ 1][ry][max(tx - 1, 0)].w;
+      const float r2 = tx >= rl ? eRight : tS[sb ^ 1][ry][min(tx + 1, 63)].x;
+      float4 out = stencil4(sc, l2, r2, tS[sb ^ 1][min(ry + 1, NY - 1)][tx],
+                            tS[sb ^ 1][max(ry - 1, 0)][tx], s, sm);
+      sphere4((int32_t)p.loZ + iM1, out);
+      if (valid) {
+        typedef float vfloat4 __attribute__((ext_vector_type(4)));
+        vfloat4 ov = {out.x, out.y, out.z, out.w};
+        __builtin_nontemporal_store(ov, (vfloat4 *)(dcell + zoff(iM1)));
+      }
+    }
+
+    tS[sb][ry][tx] = s;
+    tT[tb ^ 1][ry + 1][tx] = cp;
+    if (stagesHalo) tT[tb ^ 1][hrow][tx] = hp;
+    __syncthreads();
+    tb ^= 1;
+    sb ^= 1;
+    cm = cc;
+    cc = cp;
+    l = ln;
+    r = rn;
+    sm = sc;
+    sc = s;
+    qxp = nxp;
+    qxm = nxm;
+    qyp = nyp;
+    qym = nym;
+    qzp = nzp;
+    qzm = nzm;
+    iM1 = i0;
+    i0 = iP1;
+    iP1 = iP2;
+    iP2 = iP3;
+    iP3 = iP3 + 1 == p.extZ ? 0 : iP3 + 1;
+  };
+  // planes lz0-1 .. zEnd: the count is uniform per block, so is the branch
+  for (int32_t zz = lz0 - 1; zz <= zEnd; zz += 2) {
+    iteration(zz, vA, hA);
+    if (zz + 1 <= zEnd) iteration(zz + 1, vB, hB);
+  }
+}
+
 __global__ void jacobi_kernel(JacobiParams p) {
   const char *srcBase = p.src;
   char *dstBase = p.dst;
@@ -677,6 +941,80 @@ bool jacobi_wrap_eligible(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 
   return jac_use_lds() && row_extension(d, qi, region, /*mode=*/1, under, over);
 }
 
+// Rows per block of jacobi_kernel_fuse2 (6 of them useful). 8 rows are 8
+// waves and 36 KB of LDS, so two blocks share a CU and one computes while
+// the other waits at its barrier; 14 rows (12 useful, 14% instead of 25%
+// redundant stage-1 rows, but one block per CU) measured 12% slower.
+constexpr int JAC_F2_NY = 8;
+
+// planes per block of the fused kernel; STENCIL_JAC_F2ZC overrides (read once)
+int jac_f2_zc() {
+  static int zc = 0;
+  if (!zc) {
+    const char *e = getenv("STENCIL_JAC_F2ZC");
+    const int v = e ? atoi(e) : 0;
+    zc = v >= 1 ? v : 64;
+  }
+  return zc;
+}
+
+dim3 jac_f2_grid(int64_t extXvec, int64_t extY, int64_t extZ) {
+  const int zc = jac_f2_zc(), ny = JAC_F2_NY;
+  return dim3((uint32_t)((extXvec / 4 + 63) / 64), (uint32_t)((extY + ny - 3) / (ny - 2)),
+              (uint32_t)((extZ + zc - 1) / zc));
+}
+
+// Whether a wrap graph may replay the fused two-step kernel. The kernel
+// serves every geometry the WRAP kernel serves (the wraps are true modulos),
+// so what remains is the switch and the grid limits. STENCIL_JAC_FUSE2=0
+// forces single-step replays (the A/B lever); read at each graph creation.
+bool jacobi_fuse2_eligible(bool wrap, const LocalDomain &d, int64_t qi, const Rect3 &region) {
+  if (!wrap) return false;
+  const char *e = getenv("STENCIL_JAC_FUSE2");
+  if (e && e[0] == '0') return false;
+  int64_t under, over;
+  if (!row_extension(d, qi, region, /*mode=*/1, under, over)) return false;
+  const Vec3 ext = region.extent();
+  const dim3 g = jac_f2_grid(ext.x + under + over, ext.y, ext.z);
+  return g.y <= 65535 && g.z <= 65535;
+}
+
+// the fused kernel over the whole (row-extended) domain, curr -> next
+void launch_jacobi_fuse2_on(LocalDomain &d, int64_t qi, const Rect3 &region,
+                            const Rect3 &computeRegion, hipStream_t stream) {
+  const Vec3 ext = region.extent();
+  int64_t under, over;
+  if (!row_extension(d, qi, region, /*mode=*/1, under, over))
+    throw std::runtime_error("jacobi: fused launch needs the row extension");
+  JacobiWrapParams p{};
+  p.src = d.curr(qi).ptr;
+  p.dst = d.next(qi).ptr;
+  p.pitch = d.curr(qi).pitch;
+  p.plane = d.curr(qi).plane();
+  const Rect3 full = d.full_region();
+  p.allocX = full.lo.x;
+  p.allocY = full.lo.y;
+  p.allocZ = full.lo.z;
+  p.loX = region.lo.x - under;
+  p.loY = region.lo.y;
+  p.loZ = region.lo.z;
+  p.extX = (int32_t)(ext.x + under + over);
+  p.extY = (int32_t)ext.y;
+  p.extZ = (int32_t)ext.z;
+  p.vecAll = 1;
+  p.cLoX = computeRegion.lo.x;
+  p.cLoY = computeRegion.lo.y;
+  p.cLoZ = computeRegion.lo.z;
+  p.cHiX = computeRegion.hi.x;
+  p.cHiY = computeRegion.hi.y;
+  p.cHiZ = computeRegion.hi.z;
+  p.trueLoX = region.lo.x;
+  p.trueExtX = (int32_t)ext.x;
+  const dim3 grid = jac_f2_grid(p.extX, ext.y, ext.z);
+  hipLaunchKernelGGL(jacobi_kernel_fuse2<JAC_F2_NY>, grid, dim3(64, JAC_F2_NY, 1), 0, stream, p);
+  STENCIL_HIP(hipGetLastError());
+}
+
 } // namespace
 
 std::unique_ptr<JacobiStepGraph> jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi,
@@ -731,20 +1069,37 @@ JacobiStepGraph::JacobiStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const
     d.swap(); // bake the other parity's kernarg pointers next round
   }
   // two swaps: host+device state is back where it started
+  //
+  // Fused pairs (jacobi_fuse2_eligible): a second graph per parity holds
+  // jacobi_kernel_fuse2 alone, curr(t) -> next(t+2). A replay of it is ONE
+  // buffer swap like a single step, so after it the buffer that was `next`
+  // is current and holds t+2, while the new `next` still holds time t (not
+  // t+1, which never reaches memory).
+  fused2_ = jacobi_fuse2_eligible(wrap_, d, qi, region);
+  if (fused2_) {
+    for (int par = 0; par < 2; ++par) {
+      exec2_[par] = capture([&] { launch_jacobi_fuse2_on(d, qi, region, computeRegion, stream_); });
+      d.swap();
+    }
+  }
 }
 
 void JacobiStepGraph::launch(int64_t nSteps) {
   LocalDomain &d = domain();
   STENCIL_HIP(hipSetDevice(dev_));
-  for (int64_t i = 0; i < nSteps; ++i) {
-    STENCIL_HIP(hipGraphLaunch(exec_[parity_], stream_));
+  // run(n >= 2) on a fused graph: n/2 two-step replays, then one single
+  // step if n is odd. step() (n == 1) is always the single-step kernel.
+  const int64_t nPairs = fused2_ ? nSteps / 2 : 0;
+  const int64_t nSingle = nSteps - 2 * nPairs;
+  for (int64_t i = 0; i < nPairs + nSingle; ++i) {
+    STENCIL_HIP(hipGraphLaunch(i < nPairs ? exec2_[parity_] : exec_[parity_], stream_));
     parity_ ^= 1;
     d.swap_host_only(); // in-graph kernel flips the device tables
   }
-  // the wrap graph has no swap node (nothing in it reads the tables): an
-  // even number of flips cancels, an odd one is ONE flip, enqueued behind
+  // the wrap graphs have no swap node (nothing in them reads the tables):
+  // an even number of flips cancels, an odd one is ONE flip, enqueued behind
   // the replays so host and device state agree in stream order on return
-  if (wrap_ && (nSteps & 1)) d.enqueue_table_swap(stream_);
+  if (wrap_ && ((nPairs + nSingle) & 1)) d.enqueue_table_swap(stream_);
 }
 
 // Multi-rank whole-step graphs (one rank, one domain, cross-rank halos
@@ -827,6 +1182,35 @@ void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, flo
                      eng.compute_stream(dom), base, pp.pitch, pp.plane(), (int32_t)ext.x,
                      (int32_t)ext.y, (int32_t)ext.z, value);
   STENCIL_HIP(hipGetLastError());
+}
+
+namespace {
+
+__global__ void div6_kernel(const float *in, float *out, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    out[i] = div6(in[i]);
+}
+
+} // namespace
+
+void div6_f32(const float *in, float *out, int64_t n) {
+  if (n <= 0) return;
+  float *dIn = nullptr, *dOut = nullptr;
+  STENCIL_HIP(hipMalloc(&dIn, n * sizeof(float)));
+  if (hipMalloc(&dOut, n * sizeof(float)) != hipSuccess) {
+    (void)hipFree(dIn);
+    throw std::runtime_error("div6_f32: out of device memory");
+  }
+  hipError_t err = hipMemcpy(dIn, in, n * sizeof(float), hipMemcpyHostToDevice);
+  if (err == hipSuccess) {
+    hipLaunchKernelGGL(div6_kernel, dim3(grid_for(n, 256)), dim3(256), 0, nullptr, dIn, dOut, n);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipMemcpy(out, dOut, n * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(dIn);
+  (void)hipFree(dOut);
+  STENCIL_HIP(err);
 }
 
 } // namespace stencil_amd

@@ -5,6 +5,7 @@
 //   xz       : x + rolled z neighbors only (no y-row loads)
 //   full     : the real 7-point stencil
 //   full8    : 8 cells per thread (2 float4 strips)
+//   fuse2-NY : two time steps per pass, 64 x NY tile (see probe_fuse2)
 // Usage: jacobi_probe [n=752] [rounds=10]
 #include <algorithm>
 #include <cstdio>
@@ -276,6 +277,108 @@ __global__ void __launch_bounds__(256) probe_prod(P p, const char *const *srcSlo
   }
 }
 
+// Two time steps per pass, the tile structure of the production
+// jacobi_kernel_fuse2 (csrc/src/jacobi.hip) without its periodic wrap and
+// sphere sources: a 64 x NY block marching a chunk of zc planes computes
+// stage 1 (t+1) for all NY rows and stage 2 (t+2) for the inner NY-2; the t
+// rows and the t+1 rows sit in ping-pong LDS, the z planes of both stages
+// roll in registers, vector loads run two planes ahead. Lanes 0 / 1 of a row
+// compute the one t+1 cell just outside each x edge of the tile. Reads reach
+// 2 cells past the region on every side (the probe's 3-cell margin).
+// Usage of the variants: fuse2-8 / fuse2-14 = NY, zc = 64 planes.
+template <int NY>
+__global__ void __launch_bounds__(64 * NY) probe_fuse2(P p, int32_t zc) {
+  __shared__ float4 tT[2][NY + 2][64];
+  __shared__ float4 tS[2][NY][64];
+  const int32_t tx = threadIdx.x, ry = threadIdx.y;
+  const int32_t ub = blockIdx.x * 64;
+  const int32_t u0 = ub + tx;
+  const int32_t u = min(u0, p.nx4 - 1);
+  const int32_t yb = (int32_t)blockIdx.y * (NY - 2) - 1 + ry; // -1 .. ny: inside the margin
+  const int32_t y = min(yb, p.ny);
+  const bool valid = u0 < p.nx4 && ry >= 1 && ry <= NY - 2 && yb < p.ny;
+  const int32_t z0 = blockIdx.z * zc;
+  const int32_t zEnd = min(z0 + zc, p.nz);
+  const int64_t rowOff = (int64_t)(y + 3) * p.pitch + 16;
+  const char *cell = p.src + 3 * p.plane + rowOff + u * 16; // plane 0 of the region
+  const char *hcell = cell + (ry == 0 ? -p.pitch : ry == NY - 1 ? p.pitch : 0);
+  const bool stagesHalo = ry == 0 || ry == NY - 1;
+  const int32_t hrow = ry == 0 ? 0 : NY + 1;
+  char *dcell = p.dst + 3 * p.plane + rowOff + u * 16;
+  const int32_t rl = min(63, p.nx4 - 1 - ub);
+  // cell index (floats from the row's first vector) of the edge cell
+  const int32_t eE = tx == 0 ? ub * 4 - 1 : (ub + rl + 1) * 4;
+  const char *erow = p.src + 3 * p.plane + rowOff + eE * 4;
+  const int32_t zLast = p.nz + 2; // last plane inside the allocation
+  auto zoff = [&](int32_t z) { return (int64_t)min(z, zLast) * p.plane; };
+  auto stencil4 = [&](const float4 &c, float l, float r, const float4 &py, const float4 &my,
+                      const float4 &pz, const float4 &mz) {
+    float4 s;
+    s.x = (c.y + l + py.x + my.x + pz.x + mz.x) / 6.0f;
+    s.y = (c.z + c.x + py.y + my.y + pz.y + mz.y) / 6.0f;
+    s.z = (c.w + c.y + py.z + my.z + pz.z + mz.z) / 6.0f;
+    s.w = (r + c.z + py.w + my.w + pz.w + mz.w) / 6.0f;
+    return s;
+  };
+  int32_t zi = z0 - 1; // plane of stage 1
+  float4 cm = *(const float4 *)(cell + zoff(zi - 1));
+  float4 cc = *(const float4 *)(cell + zoff(zi));
+  float l = *(const float *)(cell + zoff(zi) - 4);
+  float r = *(const float *)(cell + zoff(zi) + 16);
+  tT[0][ry + 1][tx] = cc;
+  if (stagesHalo) tT[0][hrow][tx] = *(const float4 *)(hcell + zoff(zi));
+  float4 vA = *(const float4 *)(cell + zoff(zi + 1)), hA = *(const float4 *)(hcell + zoff(zi + 1));
+  float4 vB = *(const float4 *)(cell + zoff(zi + 2)), hB = *(const float4 *)(hcell + zoff(zi + 2));
+  float4 sm = {0.f, 0.f, 0.f, 0.f}, sc = sm;
+  float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f, q4 = 0.f, q5 = 0.f;
+  __syncthreads();
+  int tb = 0, sb = 0;
+  auto iteration = [&](int32_t zz, float4 &v, float4 &h) {
+    const float4 cp = v, hp = h;
+    const float ln = *(const float *)(cell + zoff(zz + 1) - 4);
+    const float rn = *(const float *)(cell + zoff(zz + 1) + 16);
+    const float n0 = *(const float *)(erow + zoff(zz) + 4);
+    const float n1 = *(const float *)(erow + zoff(zz) - 4);
+    const float n2 = *(const float *)(erow + zoff(zz) + p.pitch);
+    const float n3 = *(const float *)(erow + zoff(zz) - p.pitch);
+    const float n4 = *(const float *)(erow + zoff(zz + 1));
+    const float n5 = *(const float *)(erow + zoff(zz - 1));
+    v = *(const float4 *)(cell + zoff(zz + 3));
+    h = *(const float4 *)(hcell + zoff(zz + 3));
+    const float4 s = stencil4(cc, l, r, tT[tb][ry + 2][tx], tT[tb][ry][tx], cp, cm);
+    if (zz > z0) {
+      float e1 = 0.f;
+      if (tx < 2) e1 = (q0 + q1 + q2 + q3 + q4 + q5) / 6.0f;
+      const float eRight = __shfl(e1, 1);
+      const float l2 = tx == 0 ? e1 : tS[sb ^ 1][ry][max(tx - 1, 0)].w;
+      const float r2 = tx >= rl ? eRight : tS[sb ^ 1][ry][min(tx + 1, 63)].x;
+      const float4 out = stencil4(sc, l2, r2, tS[sb ^ 1][min(ry + 1, NY - 1)][tx],
+                                  tS[sb ^ 1][max(ry - 1, 0)][tx], s, sm);
+      if (valid) {
+        vfloat4 ov = {out.x, out.y, out.z, out.w};
+        __builtin_nontemporal_store(ov, (vfloat4 *)(dcell + zoff(zz - 1)));
+      }
+    }
+    tS[sb][ry][tx] = s;
+    tT[tb ^ 1][ry + 1][tx] = cp;
+    if (stagesHalo) tT[tb ^ 1][hrow][tx] = hp;
+    __syncthreads();
+    tb ^= 1;
+    sb ^= 1;
+    cm = cc;
+    cc = cp;
+    l = ln;
+    r = rn;
+    sm = sc;
+    sc = s;
+    q0 = n0, q1 = n1, q2 = n2, q3 = n3, q4 = n4, q5 = n5;
+  };
+  for (int32_t zz = z0 - 1; zz <= zEnd; zz += 2) {
+    iteration(zz, vA, hA);
+    if (zz + 1 <= zEnd) iteration(zz + 1, vB, hB);
+  }
+}
+
 int main(int argc, char **argv) {
   const int n = argc > 1 ? atoi(argv[1]) : 752;
   const int rounds = argc > 2 ? atoi(argv[2]) : 10;
@@ -309,10 +412,13 @@ int main(int argc, char **argv) {
 
   const int64_t n16 = p.plane * n / 16;
   dim3 grdsw(grd.x, grd.z, grd.y);
-  const int NV = 11;
+  const int f2zc = 64;
+  dim3 grdf8((p.nx4 + 63) / 64, (p.ny + 5) / 6, (p.nz + f2zc - 1) / f2zc);
+  dim3 grdf14((p.nx4 + 63) / 64, (p.ny + 11) / 12, (p.nz + f2zc - 1) / f2zc);
+  const int NV = 13;
   const char *names[NV] = {"copy", "xz",   "full",    "full8",   "prod-notail",
                            "prod+sph+tail", "prod+tail", "linstream", "full-plainst", "full-dispswap",
-                           "full-ldsrows"};
+                           "full-ldsrows", "fuse2-8", "fuse2-14"};
   double best[NV];
   for (int v = 0; v < NV; ++v) best[v] = 1e30;
   for (int r = 0; r < rounds; ++r) {
@@ -326,6 +432,8 @@ int main(int argc, char **argv) {
       case 8: hipLaunchKernelGGL(probe<3>, grd, blk, 0, 0, p); break;
       case 9: hipLaunchKernelGGL(probe_swap, grdsw, blk, 0, 0, p); break;
       case 10: hipLaunchKernelGGL(probe_lds, grd, blk, 0, 0, p); break;
+      case 11: hipLaunchKernelGGL(probe_fuse2<8>, grdf8, dim3(64, 8, 1), 0, 0, p, f2zc); break;
+      case 12: hipLaunchKernelGGL(probe_fuse2<14>, grdf14, dim3(64, 14, 1), 0, 0, p, f2zc); break;
       case 3: hipLaunchKernelGGL(probe8, grd8, blk, 0, 0, p); break;
       case 4:
         hipLaunchKernelGGL(probe_prod, grdp, blk, 0, 0, p, (const char *const *)slots,
@@ -349,8 +457,10 @@ int main(int argc, char **argv) {
   }
   for (int v = 0; v < NV; ++v) {
     const double bytes = (v == 7) ? 2.0 * n16 * 16 : cells * 8; // linstream: full alloc R+W
+    // fuse2-*: one pass is two updates of every cell (TB/s stays per pass)
+    const double updates = v >= 11 ? 2 * cells : cells;
     printf("%-14s %8.3f ms  %7.1f Gcell/s  %6.2f TB/s\n", names[v], best[v],
-           cells / best[v] / 1e6, bytes / best[v] / 1e9);
+           updates / best[v] / 1e6, bytes / best[v] / 1e9);
   }
   return 0;
 }

@@ -100,6 +100,13 @@ class Jacobi3D:
         # region that includes halo cells shows old values there. With a
         # non-periodic face the graph is [translate -> boundary fill ->
         # jacobi -> swap] as before.
+        # The wrap graph also holds a fused two-step kernel: run(n)
+        # replays n // 2 of those (one pass over memory per two steps,
+        # the intermediate step never reaches memory) and one single
+        # step if n is odd; step() is always a single step. Each replay
+        # is one buffer swap, so after a fused pair the NEXT buffer holds
+        # time t, not t+1. Same bits as single steps;
+        # STENCIL_JAC_FUSE2=0 forces single-step replays.
         import os
 
         self._graph = None
