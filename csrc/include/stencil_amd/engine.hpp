@@ -262,7 +262,7 @@ public:
     double *host = nullptr;
     hipStream_t stream = nullptr; // stream of the reduction in flight
     int count = 0;                // its number of partials per value (0: empty region)
-    int values = 1;               // its number of values; 1 whenever none is in flight
+    int values = 1;               // its number of values; every *_begin sets it
     bool pending = false;
   };
   // allocate = false: the bookkeeping only (an empty region launches nothing)

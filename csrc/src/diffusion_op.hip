@@ -65,6 +65,7 @@
 
 #include "stencil_amd/domain.hpp"
 #include "stencil_amd/engine.hpp"
+#include "stencil_amd/field_op.hpp"
 #include "stencil_amd/hip_check.hpp"
 #include "stencil_amd/ops.hpp"
 
@@ -97,16 +98,6 @@ const StripShape &strip_shape() {
   }();
   return s;
 }
-
-template <typename T> struct Strip;
-template <> struct Strip<float> {
-  static constexpr int N = 4;
-  typedef float vec __attribute__((ext_vector_type(4)));
-};
-template <> struct Strip<double> {
-  static constexpr int N = 2;
-  typedef double vec __attribute__((ext_vector_type(2)));
-};
 
 template <typename T> struct DiffParams {
   const char *u; // the region's first cell in curr[src]
@@ -270,13 +261,6 @@ __global__ void __launch_bounds__(256) diffusion_cells_kernel(DiffParams<T> p) {
     diffusion_cells<T, int64_t, DIAG>(p);
 }
 
-uint32_t grid_for(int64_t total, int block) {
-  int64_t g = (total + block - 1) / block;
-  // cap: 256 CUs x 16 blocks keeps the chip full while bounding launch size
-  g = std::min<int64_t>(g, 256 * 16);
-  return (uint32_t)std::max<int64_t>(g, 1);
-}
-
 template <typename T>
 void launch_diffusion(DiffParams<T> p, const Vec3 &ext, bool diag, hipStream_t stream) {
   constexpr int N = Strip<T>::N;
@@ -292,9 +276,7 @@ void launch_diffusion(DiffParams<T> p, const Vec3 &ext, bool diag, hipStream_t s
                        p.pitch % 16 == 0 && ((uintptr_t)p.u % sizeof(T)) == 0 &&
                        (ext.y + kBy - 1) / kBy <= 65535 && (ext.z + kZc - 1) / kZc <= 65535;
   if (ext.x >= 8 && stripOk) {
-    // head = cells until the next 16 B-aligned ADDRESS
-    const int64_t headAl = (int64_t)((16 - au) & 15) / (int64_t)sizeof(T);
-    p.head = (int32_t)std::min<int64_t>(headAl, ext.x);
+    p.head = (int32_t)std::min<int64_t>(head_cells(p.u, sizeof(T)), ext.x);
     p.zc = kZc;
     // strips + one lane per head / tail cell
     const int64_t units = ext.x - ((ext.x - p.head) / N) * (N - 1);
@@ -312,55 +294,28 @@ void launch_diffusion(DiffParams<T> p, const Vec3 &ext, bool diag, hipStream_t s
 void run(const char *op, ExchangeEngine &eng, int dom, int64_t uQ, int64_t kQ, int64_t outQ,
          bool outNext, const Rect3 &region, const double h[3], double sigma, double omega,
          int64_t wantEs, int streamId) {
-  const std::string name(op);
   const bool diag = uQ < 0;
-  if (dom < 0 || dom >= eng.num_domains())
-    throw std::invalid_argument(name + ": no such domain " + std::to_string(dom));
-  LocalDomain &d = eng.domain(dom);
-  const int64_t qs[3] = {diag ? kQ : uQ, kQ, outQ};
-  for (int64_t q : qs)
-    if (q < 0 || q >= d.num_data()) throw std::invalid_argument(name + ": no such quantity");
-  const int64_t es = d.elem_size(kQ);
-  if (es != 4 && es != 8)
-    throw std::invalid_argument(name + ": float32/float64 quantities only (element size " +
-                                std::to_string(es) + ")");
-  for (int64_t q : qs)
-    if (d.elem_size(q) != es)
-      throw std::invalid_argument(name + ": quantities differ in element size");
+  LocalDomain &d = checked_domain(op, eng, dom);
+  const std::initializer_list<Operand> operands = {{diag ? kQ : uQ, false}, {kQ, false}, {outQ, outNext}};
+  const int64_t es = checked_elem_size(op, d, operands);
   if (wantEs != 0 && es != wantEs)
-    throw std::invalid_argument(name + ": element size of the quantities does not match the type");
+    throw std::invalid_argument(std::string(op) + ": element size of the quantities does not match the type");
   if (streamId != 0 && streamId != 1)
-    throw std::invalid_argument(name + ": stream id must be 0 or 1");
+    throw std::invalid_argument(std::string(op) + ": stream id must be 0 or 1");
+  if (!checked_extent(op, region)) return; // empty region: no-op
   const Vec3 ext = region.extent();
-  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return; // empty region: no-op
-  if (ext.x > 0x7fffffff || ext.y > 0x7fffffff || ext.z > 0x7fffffff)
-    throw std::invalid_argument(name + ": region extent exceeds 2^31 - 1");
   const Rect3 full = d.full_region();
-  if (region.lo.x < full.lo.x || region.lo.y < full.lo.y || region.lo.z < full.lo.z ||
-      region.hi.x > full.hi.x || region.hi.y > full.hi.y || region.hi.z > full.hi.z)
-    throw std::invalid_argument(name + ": region " + region.str() +
-                                " is outside the allocation " + full.str());
-  if (region.lo.x - 1 < full.lo.x || region.lo.y - 1 < full.lo.y || region.lo.z - 1 < full.lo.z ||
-      region.hi.x + 1 > full.hi.x || region.hi.y + 1 > full.hi.y || region.hi.z + 1 > full.hi.z)
-    throw std::invalid_argument(name + ": the 1-cell face apron of region " + region.str() +
-                                " leaves the allocation " + full.str());
-  const Pitched &pu = d.curr(qs[0]);
-  const Pitched &pk = d.curr(kQ);
-  const Pitched &pd = outNext ? d.next(outQ) : d.curr(outQ);
-  if (pu.pitch != pk.pitch || pu.ysize != pk.ysize || pu.pitch != pd.pitch ||
-      pu.ysize != pd.ysize)
-    throw std::invalid_argument(name + ": quantity layouts differ");
-  const Vec3 pos = region.lo - full.lo; // allocation coords
-  const int64_t off = pos.z * pu.plane() + pos.y * pu.pitch + pos.x * es;
+  check_inside(op, "region", region, full, 1); // the kernels read the six face neighbours
+  const RegionCells c = region_cells(op, d, operands, region.lo - full.lo, es);
   STENCIL_HIP(hipSetDevice(d.gpu()));
   hipStream_t stream = eng.compute_stream(dom, streamId);
   auto fill = [&](auto &p) {
     typedef decltype(p.sigma) T;
-    p.u = pu.ptr + off;
-    p.k = pk.ptr + off;
-    p.dst = pd.ptr + off;
-    p.pitch = pu.pitch;
-    p.plane = pu.plane();
+    p.u = c.ptr[0];
+    p.k = c.ptr[1];
+    p.dst = c.ptr[2];
+    p.pitch = c.pitch;
+    p.plane = c.plane;
     p.extX = (int32_t)ext.x;
     p.extY = (int32_t)ext.y;
     p.extZ = (int32_t)ext.z;

@@ -36,10 +36,10 @@
 #include <initializer_list>
 #include <stdexcept>
 #include <string>
-#include <vector>
 
 #include "stencil_amd/domain.hpp"
 #include "stencil_amd/engine.hpp"
+#include "stencil_amd/field_op.hpp"
 #include "stencil_amd/hip_check.hpp"
 #include "stencil_amd/ops.hpp"
 
@@ -52,9 +52,7 @@ constexpr int kMinZc = 4;             // coarse planes per thread, when the regi
 constexpr int64_t kMaxGridYZ = 65535; // HIP's limit on gridDim.y and gridDim.z
 constexpr int64_t kMaxCellBlocks = 1 << 16;
 
-typedef float F2 __attribute__((ext_vector_type(2)));
-typedef float F4 __attribute__((ext_vector_type(4)));
-typedef double D2 __attribute__((ext_vector_type(2)));
+typedef float F2 __attribute__((ext_vector_type(2))); // next to field_op.hpp's F4 and D2
 // the same vectors as memory operands at ELEMENT alignment
 typedef F2 F2e __attribute__((aligned(4)));
 typedef F4 F4e __attribute__((aligned(4)));
@@ -209,11 +207,6 @@ __global__ void __launch_bounds__(256)
 
 //// host ////
 
-struct Operand {
-  int64_t q;
-  bool next;
-};
-
 struct Launch {
   LocalDomain *fd = nullptr, *cd = nullptr;
   bool empty = false;
@@ -221,77 +214,39 @@ struct Launch {
   int64_t es = 0;
   Geom g{};
   dim3 grid, block;
-  std::vector<char *> fptr, cptr; // each operand's first cell of its region
+  RegionCells f, c; // each operand's first cell of its region
 };
-
-bool inside(const Rect3 &r, const Rect3 &full) {
-  return r.lo.x >= full.lo.x && r.lo.y >= full.lo.y && r.lo.z >= full.lo.z &&
-         r.hi.x <= full.hi.x && r.hi.y <= full.hi.y && r.hi.z <= full.hi.z;
-}
 
 // Validate and shape one op. Throws std::invalid_argument before anything
 // is launched.
 Launch plan(const char *op, ExchangeEngine &fine, int fdom, std::initializer_list<Operand> fops,
             ExchangeEngine &coarse, int cdom, std::initializer_list<Operand> cops,
             const Rect3 &region) {
-  const std::string name(op);
-  if (fdom < 0 || fdom >= fine.num_domains())
-    throw std::invalid_argument(name + ": no such fine domain " + std::to_string(fdom));
-  if (cdom < 0 || cdom >= coarse.num_domains())
-    throw std::invalid_argument(name + ": no such coarse domain " + std::to_string(cdom));
   Launch l;
-  l.fd = &fine.domain(fdom);
-  l.cd = &coarse.domain(cdom);
-  for (int side = 0; side < 2; ++side) {
-    const LocalDomain &d = side == 0 ? *l.fd : *l.cd;
-    for (const Operand &o : (side == 0 ? fops : cops)) {
-      if (o.q < 0 || o.q >= d.num_data()) throw std::invalid_argument(name + ": no such quantity");
-      const int64_t es = d.elem_size(o.q);
-      if (es != 4 && es != 8)
-        throw std::invalid_argument(name + ": float32/float64 quantities only (element size " +
-                                    std::to_string(es) + ")");
-      if (l.es != 0 && es != l.es)
-        throw std::invalid_argument(name + ": operands differ in element size");
-      l.es = es;
-    }
-  }
+  l.fd = &checked_domain(op, fine, fdom, "fine domain");
+  l.cd = &checked_domain(op, coarse, cdom, "coarse domain");
+  l.es = checked_elem_size(op, *l.fd, fops);
+  l.es = checked_elem_size(op, *l.cd, cops, 0, l.es);
   if (l.fd->gpu() != l.cd->gpu())
-    throw std::invalid_argument(name + ": the fine domain is on device " +
+    throw std::invalid_argument(std::string(op) + ": the fine domain is on device " +
                                 std::to_string(l.fd->gpu()) + ", the coarse one on device " +
                                 std::to_string(l.cd->gpu()));
-  const Vec3 ext = region.extent();
-  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) {
+  if (!checked_extent(op, region, 0x3fffffff)) { // the fine extent is twice this one
     l.empty = true;
     return l;
   }
-  if (ext.x > 0x3fffffff || ext.y > 0x3fffffff || ext.z > 0x3fffffff)
-    throw std::invalid_argument(name + ": region extent exceeds 2^30 - 1");
+  const Vec3 ext = region.extent();
   const Rect3 cfull = l.cd->full_region(), ffull = l.fd->full_region();
-  if (!inside(region, cfull))
-    throw std::invalid_argument(name + ": coarse region " + region.str() +
-                                " is outside the coarse allocation " + cfull.str());
+  check_inside(op, "coarse region", region, cfull);
   const Rect3 fregion(Vec3(2 * region.lo.x, 2 * region.lo.y, 2 * region.lo.z),
                       Vec3(2 * region.hi.x, 2 * region.hi.y, 2 * region.hi.z));
-  if (!inside(fregion, ffull))
-    throw std::invalid_argument(name + ": fine region " + fregion.str() +
-                                " is outside the fine allocation " + ffull.str());
-  const Vec3 cpos = region.lo - cfull.lo, fpos = fregion.lo - ffull.lo; // allocation coords
-  for (int side = 0; side < 2; ++side) {
-    const LocalDomain &d = side == 0 ? *l.fd : *l.cd;
-    const auto &ops = side == 0 ? fops : cops;
-    const Vec3 &pos = side == 0 ? fpos : cpos;
-    const Operand &o0 = *ops.begin();
-    const Pitched &first = o0.next ? d.next(o0.q) : d.curr(o0.q);
-    for (const Operand &o : ops) {
-      const Pitched &pp = o.next ? d.next(o.q) : d.curr(o.q);
-      if (pp.pitch != first.pitch || pp.ysize != first.ysize)
-        throw std::invalid_argument(name + ": operand layouts differ");
-      (side == 0 ? l.fptr : l.cptr)
-          .push_back(pp.ptr + pos.z * pp.plane() + pos.y * pp.pitch + pos.x * l.es);
-    }
-    (side == 0 ? l.g.fPitch : l.g.cPitch) = first.pitch;
-    (side == 0 ? l.g.fPlane : l.g.cPlane) = first.plane();
-  }
+  check_inside(op, "fine region", fregion, ffull);
+  l.f = region_cells(op, *l.fd, fops, fregion.lo - ffull.lo, l.es);
+  l.c = region_cells(op, *l.cd, cops, region.lo - cfull.lo, l.es);
+  l.g.fPitch = l.f.pitch;
+  l.g.fPlane = l.f.plane;
+  l.g.cPitch = l.c.pitch;
+  l.g.cPlane = l.c.plane;
   l.g.extX = (int32_t)ext.x;
   l.g.extY = (int32_t)ext.y;
   l.g.extZ = (int32_t)ext.z;
@@ -335,11 +290,11 @@ void grid_restrict(ExchangeEngine &fine, int fdom, double alpha, int64_t a, bool
   hipStream_t stream = coarse.compute_stream(cdom, streamId);
   if (l.es == 4) {
     const float al = (float)alpha, be = (float)beta; // the one rounding to the quantity's type
-    GRID_TRANSFER_LAUNCH(float, l, grid_restrict_kernel, stream, l.g, (const char *)l.fptr[0],
-                         (const char *)l.fptr[1], l.cptr[0], al, be);
+    GRID_TRANSFER_LAUNCH(float, l, grid_restrict_kernel, stream, l.g, (const char *)l.f.ptr[0],
+                         (const char *)l.f.ptr[1], l.c.ptr[0], al, be);
   } else {
-    GRID_TRANSFER_LAUNCH(double, l, grid_restrict_kernel, stream, l.g, (const char *)l.fptr[0],
-                         (const char *)l.fptr[1], l.cptr[0], alpha, beta);
+    GRID_TRANSFER_LAUNCH(double, l, grid_restrict_kernel, stream, l.g, (const char *)l.f.ptr[0],
+                         (const char *)l.f.ptr[1], l.c.ptr[0], alpha, beta);
   }
 }
 
@@ -352,11 +307,11 @@ void grid_prolong_add(ExchangeEngine &coarse, int cdom, int64_t src, bool srcNex
   STENCIL_HIP(hipSetDevice(l.fd->gpu()));
   hipStream_t stream = fine.compute_stream(fdom, streamId);
   if (l.es == 4)
-    GRID_TRANSFER_LAUNCH(float, l, grid_prolong_add_kernel, stream, l.g, (const char *)l.cptr[0],
-                         l.fptr[0]);
+    GRID_TRANSFER_LAUNCH(float, l, grid_prolong_add_kernel, stream, l.g, (const char *)l.c.ptr[0],
+                         l.f.ptr[0]);
   else
     GRID_TRANSFER_LAUNCH(double, l, grid_prolong_add_kernel, stream, l.g,
-                         (const char *)l.cptr[0], l.fptr[0]);
+                         (const char *)l.c.ptr[0], l.f.ptr[0]);
 }
 
 } // namespace stencil_amd

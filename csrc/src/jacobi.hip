@@ -52,6 +52,7 @@
 #include "stencil_amd/device_util.hpp"
 #include "stencil_amd/domain.hpp"
 #include "stencil_amd/engine.hpp"
+#include "stencil_amd/field_op.hpp"
 #include "stencil_amd/hip_check.hpp"
 #include "stencil_amd/ops.hpp"
 
@@ -706,13 +707,6 @@ __global__ void fill_kernel(char *base, int64_t pitch, int64_t plane,
   }
 }
 
-uint32_t grid_for(int64_t total, int block) {
-  int64_t g = (total + block - 1) / block;
-  // cap: 256 CUs x 16 blocks keeps the chip full while bounding launch size
-  g = std::min<int64_t>(g, 256 * 16);
-  return (uint32_t)std::max<int64_t>(g, 1);
-}
-
 } // namespace
 
 namespace {
@@ -727,35 +721,17 @@ bool jac_use_lds() {
   return useLds != 0;
 }
 
-bool rect_inside(const Rect3 &r, const Rect3 &full) {
-  return r.lo.x >= full.lo.x && r.lo.y >= full.lo.y && r.lo.z >= full.lo.z &&
-         r.hi.x <= full.hi.x && r.hi.y <= full.hi.y && r.hi.z <= full.hi.z;
-}
-
 // Argument check of every jacobi entry point, before anything is launched
 // or captured: the kernels read a 1-cell apron around `region`, and all of
 // it has to lie inside the allocation. An empty region is a no-op and valid.
 LocalDomain &checked_jacobi_domain(ExchangeEngine &eng, int dom, int64_t qi, const char *name) {
-  if (dom < 0 || dom >= eng.num_domains())
-    throw std::invalid_argument(std::string(name) + ": no such domain " + std::to_string(dom));
-  LocalDomain &d = eng.domain(dom);
-  if (qi < 0 || qi >= d.num_data())
-    throw std::invalid_argument(std::string(name) + ": no such quantity");
-  if (d.elem_size(qi) != 4)
-    throw std::invalid_argument(std::string(name) + ": quantity must be fp32");
+  LocalDomain &d = checked_domain(name, eng, dom);
+  checked_elem_size(name, d, {{qi, false}}, 4); // fp32
   return d;
 }
 
 void check_jacobi_region(const LocalDomain &d, const Rect3 &region, const char *name) {
-  const Vec3 ext = region.extent();
-  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return;
-  if (ext.x > 0x7fffffff || ext.y > 0x7fffffff || ext.z > 0x7fffffff)
-    throw std::invalid_argument(std::string(name) + ": region extent exceeds 2^31 - 1");
-  const Rect3 full = d.full_region();
-  const Rect3 apron(region.lo - Vec3(1, 1, 1), region.hi + Vec3(1, 1, 1));
-  if (!rect_inside(apron, full))
-    throw std::invalid_argument(std::string(name) + ": region " + region.str() +
-                                " plus its 1-cell apron leaves the allocation " + full.str());
+  if (checked_extent(name, region)) check_inside(name, "region", region, d.full_region(), 1);
 }
 
 // Row extension of a pure-vector (vecAll) launch: the x range of `region`
@@ -1165,14 +1141,10 @@ void JacobiMrStepGraph::post() {
 void fill_f32(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region, float value,
               bool nextBuf) {
   LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "fill_f32");
+  if (!checked_extent("fill_f32", region)) return;
   const Vec3 ext = region.extent();
-  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return;
-  if (ext.x > 0x7fffffff || ext.y > 0x7fffffff || ext.z > 0x7fffffff)
-    throw std::invalid_argument("fill_f32: region extent exceeds 2^31 - 1");
   const Rect3 full = d.full_region();
-  if (!rect_inside(region, full))
-    throw std::invalid_argument("fill_f32: region " + region.str() +
-                                " is outside the allocation " + full.str());
+  check_inside("fill_f32", "region", region, full);
   const Vec3 pos = region.lo - full.lo; // allocation coords
   const Pitched &pp = d.curr(qi);
   const int64_t off = pos.z * pp.plane() + pos.y * pp.pitch + pos.x * 4;

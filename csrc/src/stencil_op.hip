@@ -40,6 +40,7 @@
 
 #include "stencil_amd/domain.hpp"
 #include "stencil_amd/engine.hpp"
+#include "stencil_amd/field_op.hpp"
 #include "stencil_amd/hip_check.hpp"
 #include "stencil_amd/ops.hpp"
 
@@ -107,16 +108,6 @@ template <typename T> __global__ void __launch_bounds__(256) stencil_taps_kernel
 }
 
 //// star path ////
-
-template <typename T> struct Strip;
-template <> struct Strip<float> {
-  static constexpr int N = 4;
-  typedef float vec __attribute__((ext_vector_type(4)));
-};
-template <> struct Strip<double> {
-  static constexpr int N = 2;
-  typedef double vec __attribute__((ext_vector_type(2)));
-};
 
 template <typename T, int R> struct StarParams {
   const char *src; // the region's first cell
@@ -269,13 +260,6 @@ __global__ void __launch_bounds__(256) stencil_star_kernel(StarParams<T, R> p) {
   }
 }
 
-uint32_t grid_for(int64_t total, int block) {
-  int64_t g = (total + block - 1) / block;
-  // cap: 256 CUs x 16 blocks keeps the chip full while bounding launch size
-  g = std::min<int64_t>(g, 256 * 16);
-  return (uint32_t)std::max<int64_t>(g, 1);
-}
-
 struct StarShape {
   int bx = 64, by = 4, zc = kDefaultZc;
 };
@@ -336,10 +320,7 @@ void launch_star(const char *src, char *dst, int64_t pitch, int64_t plane, const
   p.extZ = (int32_t)ext.z;
   const StarShape &shape = star_shape();
   p.zc = shape.zc;
-  // head = cells until the next 16 B-aligned ADDRESS (the allocation pad
-  // shifts the base, so index-aligned strips would be misaligned)
-  const int64_t headAl = (int64_t)((16 - ((uintptr_t)src & 15)) & 15) / (int64_t)sizeof(T);
-  p.head = (int32_t)std::min<int64_t>(headAl, ext.x);
+  p.head = (int32_t)std::min<int64_t>(head_cells(src, sizeof(T)), ext.x);
 
   // per-axis tables in offset space, then z re-laid into slot space
   double wz[2 * R + 1] = {};
@@ -422,50 +403,32 @@ void launch_stencil(const char *src, char *dst, int64_t pitch, int64_t plane, co
 
 void stencil_apply(ExchangeEngine &eng, int dom, int64_t srcQ, int64_t dstQ, const Rect3 &region,
                    const StencilTaps &taps, StencilType type, int streamId) {
-  if (dom < 0 || dom >= eng.num_domains())
-    throw std::invalid_argument("stencil_apply: no such domain " + std::to_string(dom));
-  LocalDomain &d = eng.domain(dom);
-  const int64_t es = type == StencilType::F32 ? 4 : 8;
-  if (srcQ < 0 || srcQ >= d.num_data() || dstQ < 0 || dstQ >= d.num_data())
-    throw std::invalid_argument("stencil_apply: no such quantity");
-  if (d.elem_size(srcQ) != es || d.elem_size(dstQ) != es)
-    throw std::invalid_argument("stencil_apply: element size of the quantities does not match "
-                                "the stencil type");
+  const char *op = "stencil_apply";
+  LocalDomain &d = checked_domain(op, eng, dom);
+  const int64_t es = type == StencilType::F32 ? 4 : 8; // the stencil type's
+  checked_elem_size(op, d, {{srcQ, false}, {dstQ, true}}, es);
   const size_t ntaps = taps.offsets.size();
   if (ntaps != taps.weights.size())
     throw std::invalid_argument("stencil_apply: offsets and weights differ in length");
   if (ntaps == 0 || ntaps > (size_t)kMaxTaps)
     throw std::invalid_argument("stencil_apply: want 1.." + std::to_string(kMaxTaps) +
                                 " taps, got " + std::to_string(ntaps));
+  if (!checked_extent(op, region)) return; // empty region: no-op
   const Vec3 ext = region.extent();
-  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return; // empty region: no-op
-  if (ext.x > 0x7fffffff || ext.y > 0x7fffffff || ext.z > 0x7fffffff)
-    throw std::invalid_argument("stencil_apply: region extent exceeds 2^31 - 1");
   const Rect3 full = d.full_region();
-  for (const Vec3 &o : taps.offsets) {
-    const Vec3 lo = region.lo + o, hi = region.hi + o;
-    if (lo.x < full.lo.x || lo.y < full.lo.y || lo.z < full.lo.z || hi.x > full.hi.x ||
-        hi.y > full.hi.y || hi.z > full.hi.z)
+  for (const Vec3 &o : taps.offsets)
+    if (!rect_inside(Rect3(region.lo + o, region.hi + o), full))
       throw std::invalid_argument("stencil_apply: tap " + o.str() + " over region " +
                                   region.str() + " reads outside the allocation " + full.str());
-  }
   // a tap-free cell of the region itself must be allocated too (it is written)
-  if (region.lo.x < full.lo.x || region.lo.y < full.lo.y || region.lo.z < full.lo.z ||
-      region.hi.x > full.hi.x || region.hi.y > full.hi.y || region.hi.z > full.hi.z)
-    throw std::invalid_argument("stencil_apply: region " + region.str() +
-                                " is outside the allocation " + full.str());
-  const Pitched &ps = d.curr(srcQ);
-  const Pitched &pd = d.next(dstQ);
-  if (ps.pitch != pd.pitch || ps.ysize != pd.ysize)
-    throw std::invalid_argument("stencil_apply: source and destination layouts differ");
-  const Vec3 pos = region.lo - full.lo; // allocation coords
-  const int64_t off = pos.z * ps.plane() + pos.y * ps.pitch + pos.x * es;
+  check_inside(op, "region", region, full);
+  const RegionCells c = region_cells(op, d, {{srcQ, false}, {dstQ, true}}, region.lo - full.lo, es);
   STENCIL_HIP(hipSetDevice(d.gpu()));
   hipStream_t stream = eng.compute_stream(dom, streamId);
   if (type == StencilType::F32)
-    launch_stencil<float>(ps.ptr + off, pd.ptr + off, ps.pitch, ps.plane(), ext, taps, stream);
+    launch_stencil<float>(c.ptr[0], c.ptr[1], c.pitch, c.plane, ext, taps, stream);
   else
-    launch_stencil<double>(ps.ptr + off, pd.ptr + off, ps.pitch, ps.plane(), ext, taps, stream);
+    launch_stencil<double>(c.ptr[0], c.ptr[1], c.pitch, c.plane, ext, taps, stream);
   STENCIL_HIP(hipGetLastError());
 }
 

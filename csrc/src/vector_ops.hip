@@ -14,6 +14,17 @@
 // the 16 B strips cover aligned cells of the region only, the cells before
 // the first and after the last aligned strip of a row get a lane each.
 //
+// Structure. An op is a functor: its operands' first cells of the region,
+// its scalars in the quantity's type, and at<V>(off) for the cell(s) at
+// byte offset `off`. Two kernel templates take it by value: field_kernel
+// for the element-wise ops (axpbypcz_kernel stands in for one, see there),
+// reduce_kernel for the functors that also
+// declare NV and acc[NV], the values they sum. Two host helpers,
+// run_field and begin_reduce, do the rest (plan, empty region, device and
+// stream, the float / double dispatch with the one rounding of each scalar,
+// launch, landing the partials), so a public op is its operand list and
+// its functor.
+//
 // Two walks over the region, chosen on the host (plan_launch):
 //   strips: the star kernel's row scheme. One thread = one 16 B x strip
 //     (float4 / double2, aligned by ADDRESS) marching zc planes in z; lanes
@@ -24,10 +35,10 @@
 //     thin slabs and the unequally aligned.
 //
 // Reductions are deterministic: fp64 accumulation per thread, cross-lane
-// shuffles per wave, LDS per block, one partial per block written with an
-// ordinary store, the partials summed in index order on the host. No
-// atomics. The grid never exceeds ExchangeEngine::kReducePartials blocks;
-// the engine's per-domain scratch holds kReduceValues times as many
+// shuffles per wave, LDS per block, one partial per block and value written
+// with an ordinary store, the partials summed in index order on the host.
+// No atomics. The grid never exceeds ExchangeEngine::kReducePartials
+// blocks; the engine's per-domain scratch holds kReduceValues times as many
 // doubles, value-major (partials[v * blocks + b]), for the reductions that
 // return up to three values from one pass.
 #include <hip/hip_runtime.h>
@@ -37,10 +48,11 @@
 #include <initializer_list>
 #include <stdexcept>
 #include <string>
-#include <vector>
+#include <type_traits>
 
 #include "stencil_amd/domain.hpp"
 #include "stencil_amd/engine.hpp"
+#include "stencil_amd/field_op.hpp"
 #include "stencil_amd/hip_check.hpp"
 #include "stencil_amd/ops.hpp"
 
@@ -50,18 +62,6 @@ namespace {
 
 constexpr int kBx = 64, kBy = 4; // strip block: one wave per row, 4 rows
 constexpr int kMinZc = 4;        // planes per thread, when the region has them
-
-typedef float F4 __attribute__((ext_vector_type(4)));
-typedef double D2 __attribute__((ext_vector_type(2)));
-template <typename T> struct Strip;
-template <> struct Strip<float> {
-  static constexpr int N = 4;
-  typedef F4 vec;
-};
-template <> struct Strip<double> {
-  static constexpr int N = 2;
-  typedef D2 vec;
-};
 
 struct Geom {
   int64_t pitch, plane; // byte strides, the same for every operand
@@ -136,22 +136,6 @@ __device__ __forceinline__ void add_prod(double &acc, D2 a, D2 b) {
   for (int c = 0; c < 2; ++c) add_prod(acc, a[c], b[c]);
 }
 
-// Every thread of the 256-thread block calls this once (threads without a
-// cell bring 0): wave sums by shuffles, the 4 wave sums through LDS, one
-// ordinary store per block. A fixed order: the same bits every time.
-__device__ __forceinline__ void block_sum_store(double v, double *partials) {
-  __shared__ double sWave[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int tid = threadIdx.y * blockDim.x + threadIdx.x;
-  if ((tid & 63) == 0) sWave[tid >> 6] = v;
-  __syncthreads();
-  if (tid == 0) {
-    const int64_t b = ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[b] = ((sWave[0] + sWave[1]) + sWave[2]) + sWave[3];
-  }
-}
-
 // acc += a in fp64, component after component
 __device__ __forceinline__ void add_val(double &acc, float a) { acc += (double)a; }
 __device__ __forceinline__ void add_val(double &acc, double a) { acc += a; }
@@ -164,8 +148,10 @@ __device__ __forceinline__ void add_val(double &acc, D2 a) {
   for (int c = 0; c < 2; ++c) add_val(acc, a[c]);
 }
 
-// block_sum_store for NV values at once: value v of block b lands in
-// partials[v * blocks + b]. The same fixed order per value.
+// Every thread of the 256-thread block calls this once (threads without a
+// cell bring 0): per value, wave sums by shuffles, the 4 wave sums through
+// LDS, one ordinary store per block: value v of block b lands in
+// partials[v * blocks + b]. A fixed order: the same bits every time.
 template <int NV>
 __device__ __forceinline__ void block_store_sums(const double (&in)[NV], double *partials) {
   __shared__ double sWaves[NV][4];
@@ -187,11 +173,48 @@ __device__ __forceinline__ void block_store_sums(const double (&in)[NV], double 
   }
 }
 
-struct DotF {
+//// the ops ////
+
+// a . b; SUMS: and sum a, sum b
+template <bool SUMS> struct DotF {
+  static constexpr int NV = SUMS ? 3 : 1;
   const char *a, *b;
-  double acc;
+  double acc[NV];
   template <typename V> __device__ __forceinline__ void at(int64_t off) {
-    add_prod(acc, *(const V *)(a + off), *(const V *)(b + off));
+    const V va = *(const V *)(a + off), vb = *(const V *)(b + off);
+    add_prod(acc[0], va, vb);
+    if constexpr (SUMS) {
+      add_val(acc[1], va);
+      add_val(acc[2], vb);
+    }
+  }
+};
+
+struct SumF {
+  static constexpr int NV = 1;
+  const char *a;
+  double acc[NV];
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    add_val(acc[0], *(const V *)(a + off));
+  }
+};
+
+// x += alpha p; r -= alpha ap; r_new . r_new; SUM: and sum r_new
+template <typename T, bool SUM> struct CgF {
+  static constexpr int NV = SUM ? 2 : 1;
+  char *x;
+  const char *p, *ap;
+  char *r;
+  T alpha;
+  double acc[NV];
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vp = *(const V *)(p + off), vap = *(const V *)(ap + off);
+    const V vx = *(const V *)(x + off), vr = *(const V *)(r + off);
+    const V rn = vr - alpha * vap;
+    *(V *)(x + off) = vx + alpha * vp;
+    *(V *)(r + off) = rn;
+    add_prod(acc[0], rn, rn);
+    if constexpr (SUM) add_val(acc[1], rn);
   }
 };
 
@@ -202,6 +225,16 @@ template <typename T> struct AxpbyF {
   template <typename V> __device__ __forceinline__ void at(int64_t off) {
     const V vx = *(const V *)(x + off), vy = *(const V *)(y + off);
     *(V *)(out + off) = alpha * vx + beta * vy;
+  }
+};
+
+template <typename T> struct AxpbycF {
+  const char *x, *y;
+  char *out;
+  T alpha, beta, c;
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vx = *(const V *)(x + off), vy = *(const V *)(y + off);
+    *(V *)(out + off) = alpha * vx + beta * vy + c;
   }
 };
 
@@ -226,82 +259,35 @@ template <typename T> struct ScaledF {
   }
 };
 
-template <typename T> struct CgF {
-  char *x, *r;
-  const char *p, *ap;
-  T alpha;
-  double acc;
-  template <typename V> __device__ __forceinline__ void at(int64_t off) {
-    const V vp = *(const V *)(p + off), vap = *(const V *)(ap + off);
-    const V vx = *(const V *)(x + off), vr = *(const V *)(r + off);
-    const V rn = vr - alpha * vap;
-    *(V *)(x + off) = vx + alpha * vp;
-    *(V *)(r + off) = rn;
-    add_prod(acc, rn, rn);
-  }
-};
+// Waves per SIMD a reduction is held to; 0: the compiler's choice.
+// DotF<true> in float: the 4 x unrolled strip loop wants 74 VGPRs to keep
+// its 8 loads in flight. Held to 64 (8 waves per SIMD) the scheduler
+// serialises them, 2 in flight, and the kernel runs 5-6% behind DotF<false>;
+// at 6 waves it batches them as DotF<false> does. double fits 8 waves as it
+// is.
+template <typename F, typename T> constexpr int kWaves = 0;
+template <typename T> constexpr int kWaves<DotF<true>, T> = sizeof(T) == 4 ? 6 : 8;
 
-struct SumF {
-  const char *a;
-  double acc;
-  template <typename V> __device__ __forceinline__ void at(int64_t off) {
-    add_val(acc, *(const V *)(a + off));
-  }
-};
-
-struct DotSumsF {
-  const char *a, *b;
-  double ab, sa, sb;
-  template <typename V> __device__ __forceinline__ void at(int64_t off) {
-    const V va = *(const V *)(a + off), vb = *(const V *)(b + off);
-    add_prod(ab, va, vb);
-    add_val(sa, va);
-    add_val(sb, vb);
-  }
-};
-
-// CgF's arithmetic, statement for statement, plus sum r_new
-template <typename T> struct CgSumF {
-  char *x, *r;
-  const char *p, *ap;
-  T alpha;
-  double acc, sum;
-  template <typename V> __device__ __forceinline__ void at(int64_t off) {
-    const V vp = *(const V *)(p + off), vap = *(const V *)(ap + off);
-    const V vx = *(const V *)(x + off), vr = *(const V *)(r + off);
-    const V rn = vr - alpha * vap;
-    *(V *)(x + off) = vx + alpha * vp;
-    *(V *)(r + off) = rn;
-    add_prod(acc, rn, rn);
-    add_val(sum, rn);
-  }
-};
-
-template <typename T> struct AxpbycF {
-  const char *x, *y;
-  char *out;
-  T alpha, beta, c;
-  template <typename V> __device__ __forceinline__ void at(int64_t off) {
-    const V vx = *(const V *)(x + off), vy = *(const V *)(y + off);
-    *(V *)(out + off) = alpha * vx + beta * vy + c;
-  }
-};
-
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256)
-    dot_kernel(Geom g, const char *a, const char *b, double *partials) {
-  DotF f{a, b, 0.0};
-  walk<T, STRIPS>(g, f);
-  block_sum_store(f.acc, partials);
-}
-
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256)
-    axpby_kernel(Geom g, const char *x, const char *y, char *out, T alpha, T beta) {
-  AxpbyF<T> f{x, y, out, alpha, beta};
+template <typename T, bool STRIPS, typename F>
+__global__ void __launch_bounds__(256) field_kernel(Geom g, F f) {
   walk<T, STRIPS>(g, f);
 }
 
+template <typename T, bool STRIPS, typename F>
+__global__ void __launch_bounds__(256)
+    __attribute__((amdgpu_waves_per_eu(kWaves<F, T>, kWaves<F, T>)))
+    reduce_kernel(Geom g, F f, double *partials) {
+  // zeroed here: what the argument holds the compiler would have to load
+#pragma unroll
+  for (int k = 0; k < F::NV; ++k) f.acc[k] = 0.0;
+  walk<T, STRIPS>(g, f);
+  block_store_sums<F::NV>(f.acc, partials);
+}
+
+// AxpbypczF keeps a kernel with loose arguments. In float the bits of
+// alpha x + beta y + gamma z depend on which product the compiler contracts
+// into an fma first, and from this form it picks beta y (cells walk:
+// fma(beta, y, alpha x) + gamma z), from field_kernel alpha x.
 template <typename T, bool STRIPS>
 __global__ void __launch_bounds__(256)
     axpbypcz_kernel(Geom g, const char *x, const char *y, const char *z, char *out, T alpha,
@@ -310,68 +296,7 @@ __global__ void __launch_bounds__(256)
   walk<T, STRIPS>(g, f);
 }
 
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256)
-    scaled_update_kernel(Geom g, const char *x, const char *d, const char *y, const char *z,
-                         char *out, T alpha, T beta, T gamma) {
-  ScaledF<T> f{x, d, y, z, out, alpha, beta, gamma};
-  walk<T, STRIPS>(g, f);
-}
-
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256)
-    cg_update_kernel(Geom g, char *x, const char *p, const char *ap, char *r, T alpha,
-                     double *partials) {
-  CgF<T> f{x, r, p, ap, alpha, 0.0};
-  walk<T, STRIPS>(g, f);
-  block_sum_store(f.acc, partials);
-}
-
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256) sum_kernel(Geom g, const char *a, double *partials) {
-  SumF f{a, 0.0};
-  walk<T, STRIPS>(g, f);
-  const double v[1] = {f.acc};
-  block_store_sums<1>(v, partials);
-}
-
-// float: the 4 x unrolled strip loop wants 74 VGPRs to keep its 8 loads in
-// flight. Held to 64 (8 waves per SIMD) the scheduler serialises them, 2 in
-// flight, and the kernel runs 5-6% behind dot_kernel; at 6 waves it batches
-// them as dot_kernel does. double fits 8 waves as it is.
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256)
-    __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 6 : 8, sizeof(T) == 4 ? 6 : 8)))
-    dot_sums_kernel(Geom g, const char *a, const char *b, double *partials) {
-  DotSumsF f{a, b, 0.0, 0.0, 0.0};
-  walk<T, STRIPS>(g, f);
-  const double v[3] = {f.ab, f.sa, f.sb};
-  block_store_sums<3>(v, partials);
-}
-
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256)
-    cg_update_sum_kernel(Geom g, char *x, const char *p, const char *ap, char *r, T alpha,
-                         double *partials) {
-  CgSumF<T> f{x, r, p, ap, alpha, 0.0, 0.0};
-  walk<T, STRIPS>(g, f);
-  const double v[2] = {f.acc, f.sum};
-  block_store_sums<2>(v, partials);
-}
-
-template <typename T, bool STRIPS>
-__global__ void __launch_bounds__(256)
-    axpbyc_kernel(Geom g, const char *x, const char *y, char *out, T alpha, T beta, T c) {
-  AxpbycF<T> f{x, y, out, alpha, beta, c};
-  walk<T, STRIPS>(g, f);
-}
-
 //// host ////
-
-struct Operand {
-  int64_t q;
-  bool next;
-};
 
 struct Launch {
   LocalDomain *d = nullptr;
@@ -381,62 +306,39 @@ struct Launch {
   Geom g{};
   dim3 grid, block;
   int blocks = 0;
-  std::vector<char *> ptr; // each operand's first cell of the region
+  RegionCells c; // each operand's first cell of the region
 };
 
 // Validate and shape one op. Throws std::invalid_argument before anything
 // is launched or allocated.
 Launch plan_launch(const char *op, ExchangeEngine &eng, int dom,
                    std::initializer_list<Operand> operands, const Rect3 &region) {
-  const std::string name(op);
-  if (dom < 0 || dom >= eng.num_domains())
-    throw std::invalid_argument(name + ": no such domain " + std::to_string(dom));
   Launch l;
-  l.d = &eng.domain(dom);
-  LocalDomain &d = *l.d;
-  for (const Operand &o : operands) {
-    if (o.q < 0 || o.q >= d.num_data()) throw std::invalid_argument(name + ": no such quantity");
-    const int64_t es = d.elem_size(o.q);
-    if (es != 4 && es != 8)
-      throw std::invalid_argument(name + ": float32/float64 quantities only (element size " +
-                                  std::to_string(es) + ")");
-    if (l.es != 0 && es != l.es)
-      throw std::invalid_argument(name + ": operands differ in element size");
-    l.es = es;
-  }
-  const Vec3 ext = region.extent();
-  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) {
+  l.d = &checked_domain(op, eng, dom);
+  l.es = checked_elem_size(op, *l.d, operands);
+  if (!checked_extent(op, region)) {
     l.empty = true;
     return l;
   }
-  if (ext.x > 0x7fffffff || ext.y > 0x7fffffff || ext.z > 0x7fffffff)
-    throw std::invalid_argument(name + ": region extent exceeds 2^31 - 1");
-  const Rect3 full = d.full_region();
-  if (region.lo.x < full.lo.x || region.lo.y < full.lo.y || region.lo.z < full.lo.z ||
-      region.hi.x > full.hi.x || region.hi.y > full.hi.y || region.hi.z > full.hi.z)
-    throw std::invalid_argument(name + ": region " + region.str() +
-                                " is outside the allocation " + full.str());
-  const Vec3 pos = region.lo - full.lo; // allocation coords
-  const Pitched &first = d.curr(operands.begin()->q);
-  for (const Operand &o : operands) {
-    const Pitched &pp = o.next ? d.next(o.q) : d.curr(o.q);
-    if (pp.pitch != first.pitch || pp.ysize != first.ysize)
-      throw std::invalid_argument(name + ": operand layouts differ");
-    l.ptr.push_back(pp.ptr + pos.z * pp.plane() + pos.y * pp.pitch + pos.x * l.es);
-  }
-  l.g.pitch = first.pitch;
-  l.g.plane = first.plane();
+  const Rect3 full = l.d->full_region();
+  check_inside(op, "region", region, full);
+  l.c = region_cells(op, *l.d, operands, region.lo - full.lo, l.es);
+  const Vec3 ext = region.extent();
+  l.g.pitch = l.c.pitch;
+  l.g.plane = l.c.plane;
   l.g.extX = (int32_t)ext.x;
   l.g.extY = (int32_t)ext.y;
   l.g.extZ = (int32_t)ext.z;
 
   // strips: as launch_stencil's stripOk, over every operand pointer
   const int n = (int)(16 / l.es);
-  bool ok = ext.x >= 8 && first.pitch % 16 == 0;
-  for (char *p : l.ptr)
-    ok = ok && ((uintptr_t)p & 15) == ((uintptr_t)l.ptr[0] & 15) && ((uintptr_t)p % l.es) == 0;
+  bool ok = ext.x >= 8 && l.c.pitch % 16 == 0;
+  for (int i = 0; i < l.c.n; ++i) {
+    const uintptr_t p = (uintptr_t)l.c.ptr[i];
+    ok = ok && (p & 15) == ((uintptr_t)l.c.ptr[0] & 15) && (p % l.es) == 0;
+  }
   if (ok) {
-    const int64_t head = (int64_t)((16 - ((uintptr_t)l.ptr[0] & 15)) & 15) / l.es;
+    const int64_t head = head_cells(l.c.ptr[0], l.es);
     const int64_t units = ext.x - ((ext.x - head) / n) * (n - 1);
     const int64_t gx = (units + kBx - 1) / kBx, gy = (ext.y + kBy - 1) / kBy;
     if (gx * gy <= ExchangeEngine::kReducePartials) {
@@ -460,134 +362,146 @@ Launch plan_launch(const char *op, ExchangeEngine &eng, int dom,
   return l;
 }
 
-#define VEC_OPS_LAUNCH(T, l, KERNEL, stream, ...)                                                 \
-  do {                                                                                             \
-    if ((l).strips)                                                                                \
-      hipLaunchKernelGGL((KERNEL<T, true>), (l).grid, (l).block, 0, stream, __VA_ARGS__);          \
-    else                                                                                           \
-      hipLaunchKernelGGL((KERNEL<T, false>), (l).grid, (l).block, 0, stream, __VA_ARGS__);         \
-    STENCIL_HIP(hipGetLastError());                                                                \
-  } while (0)
+// fn(T(), std::bool_constant<STRIPS>()) with the quantity's type and the walk
+template <typename Fn> void dispatch(const Launch &l, Fn fn) {
+  auto typed = [&](auto t) {
+    if (l.strips)
+      fn(t, std::true_type());
+    else
+      fn(t, std::false_type());
+  };
+  if (l.es == 4)
+    typed(float());
+  else
+    typed(double());
+  STENCIL_HIP(hipGetLastError());
+}
 
-ExchangeEngine::ReduceScratch &begin_reduction(const char *op, ExchangeEngine &eng, int dom,
-                                               bool allocate) {
-  ExchangeEngine::ReduceScratch &sc = eng.reduce_scratch(dom, allocate);
+template <typename T, bool STRIPS, typename F>
+void launch_field(const Launch &l, hipStream_t stream, const F &f) {
+  hipLaunchKernelGGL((field_kernel<T, STRIPS, F>), l.grid, l.block, 0, stream, l.g, f);
+}
+template <typename T, bool STRIPS>
+void launch_field(const Launch &l, hipStream_t stream, const AxpbypczF<T> &f) {
+  hipLaunchKernelGGL((axpbypcz_kernel<T, STRIPS>), l.grid, l.block, 0, stream, l.g, f.x, f.y, f.z,
+                     f.out, f.alpha, f.beta, f.gamma);
+}
+
+// An element-wise op. make(T(), ptr) gives the functor over the operands'
+// first cells ptr[i], T the quantity's type: the (T) it puts on a scalar is
+// that scalar's one rounding.
+template <typename Make>
+void run_field(const char *op, ExchangeEngine &eng, int dom,
+               std::initializer_list<Operand> operands, const Rect3 &region, int streamId,
+               Make make) {
+  const Launch l = plan_launch(op, eng, dom, operands, region);
+  if (l.empty) return;
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  dispatch(l, [&](auto t, auto strips) {
+    launch_field<decltype(t), decltype(strips)::value>(l, stream, make(t, l.c.ptr));
+  });
+}
+
+// Leave a reduction of `values` values and `count` partials each in flight;
+// count > 0: the partials go to the pinned host buffer behind the kernel,
+// reduction_end_n waits. count = 0 is the empty region.
+void land(ExchangeEngine::ReduceScratch &sc, int count, int values, hipStream_t stream) {
+  if (count > 0)
+    STENCIL_HIP(hipMemcpyAsync(sc.host, sc.dev, (size_t)values * (size_t)count * sizeof(double),
+                               hipMemcpyDeviceToHost, stream));
+  sc.stream = stream;
+  sc.count = count;
+  sc.values = values;
+  sc.pending = true;
+}
+
+// A reduction: run_field with a functor that has NV and acc[NV]. Throws
+// std::runtime_error, launching nothing, while another is in flight.
+template <typename Make>
+void begin_reduce(const char *op, ExchangeEngine &eng, int dom,
+                  std::initializer_list<Operand> operands, const Rect3 &region, int streamId,
+                  Make make) {
+  const Launch l = plan_launch(op, eng, dom, operands, region);
+  ExchangeEngine::ReduceScratch &sc = eng.reduce_scratch(dom, !l.empty);
   if (sc.pending)
     throw std::runtime_error(std::string(op) + ": a reduction is already in flight on domain " +
                              std::to_string(dom) + " (call reduction_end first)");
-  return sc;
+  constexpr int NV = decltype(make(float(), l.c.ptr))::NV;
+  if (l.empty) return land(sc, 0, NV, nullptr);
+  STENCIL_HIP(hipSetDevice(l.d->gpu()));
+  hipStream_t stream = eng.compute_stream(dom, streamId);
+  dispatch(l, [&](auto t, auto strips) {
+    auto f = make(t, l.c.ptr);
+    typedef decltype(f) F;
+    static_assert(F::NV == NV && NV <= ExchangeEngine::kReduceValues, "value count");
+    hipLaunchKernelGGL((reduce_kernel<decltype(t), decltype(strips)::value, F>), l.grid, l.block, 0,
+                       stream, l.g, f, sc.dev);
+  });
+  land(sc, l.blocks, NV, stream);
 }
 
-// partials -> pinned host buffer behind the kernel; reduction_end waits
-void land_partials(ExchangeEngine::ReduceScratch &sc, int blocks, hipStream_t stream) {
-  STENCIL_HIP(hipMemcpyAsync(sc.host, sc.dev, (size_t)blocks * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-  sc.stream = stream;
-  sc.count = blocks;
-  sc.pending = true;
-}
-
-// the n-valued form: value-major partials, n * blocks doubles in one copy
-void land_partials_n(ExchangeEngine::ReduceScratch &sc, int blocks, int n, hipStream_t stream) {
-  STENCIL_HIP(hipMemcpyAsync(sc.host, sc.dev, (size_t)n * (size_t)blocks * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-  sc.stream = stream;
-  sc.count = blocks;
-  sc.values = n;
-  sc.pending = true;
-}
-
-void land_empty_n(ExchangeEngine::ReduceScratch &sc, int n) {
-  sc.count = 0;
-  sc.values = n;
-  sc.pending = true;
+void check_distinct(const char *op, int64_t x, int64_t p, int64_t r) {
+  if (x == p || x == r || p == r)
+    throw std::invalid_argument(std::string(op) + ": x, p and r must be distinct quantities");
 }
 
 } // namespace
 
 void field_dot_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
                      const Rect3 &region, int streamId) {
-  const Launch l = plan_launch("field_dot", eng, dom, {{a, aNext}, {b, bNext}}, region);
-  ExchangeEngine::ReduceScratch &sc = begin_reduction("field_dot", eng, dom, !l.empty);
-  if (l.empty) {
-    sc.count = 0;
-    sc.pending = true;
-    return;
-  }
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4)
-    VEC_OPS_LAUNCH(float, l, dot_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], sc.dev);
-  else
-    VEC_OPS_LAUNCH(double, l, dot_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], sc.dev);
-  land_partials(sc, l.blocks, stream);
+  begin_reduce("field_dot", eng, dom, {{a, aNext}, {b, bNext}}, region, streamId,
+               [](auto, char *const *p) { return DotF<false>{p[0], p[1], {}}; });
 }
 
+void field_dot_sums_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b,
+                          bool bNext, const Rect3 &region, int streamId) {
+  begin_reduce("field_dot_sums", eng, dom, {{a, aNext}, {b, bNext}}, region, streamId,
+               [](auto, char *const *p) { return DotF<true>{p[0], p[1], {}}; });
+}
+
+void field_sum_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
+                     int streamId) {
+  begin_reduce("field_sum", eng, dom, {{a, aNext}}, region, streamId,
+               [](auto, char *const *p) { return SumF{p[0], {}}; });
+}
+
+// operands of both: curr[x], curr[p], next[p] (= A p), curr[r]
 void cg_update_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
                      const Rect3 &region, int streamId) {
-  // operands: curr[x], curr[p], next[p] (= A p), curr[r]
-  const Launch l =
-      plan_launch("cg_update", eng, dom, {{x, false}, {p, false}, {p, true}, {r, false}}, region);
-  if (x == p || x == r || p == r)
-    throw std::invalid_argument("cg_update: x, p and r must be distinct quantities");
-  ExchangeEngine::ReduceScratch &sc = begin_reduction("cg_update", eng, dom, !l.empty);
-  if (l.empty) {
-    sc.count = 0;
-    sc.pending = true;
-    return;
-  }
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4) {
-    const float al = (float)alpha; // the one rounding to the quantity's type
-    VEC_OPS_LAUNCH(float, l, cg_update_kernel, stream, l.g, l.ptr[0], (const char *)l.ptr[1],
-                   (const char *)l.ptr[2], l.ptr[3], al, sc.dev);
-  } else {
-    VEC_OPS_LAUNCH(double, l, cg_update_kernel, stream, l.g, l.ptr[0], (const char *)l.ptr[1],
-                   (const char *)l.ptr[2], l.ptr[3], alpha, sc.dev);
-  }
-  land_partials(sc, l.blocks, stream);
+  check_distinct("cg_update", x, p, r);
+  begin_reduce("cg_update", eng, dom, {{x, false}, {p, false}, {p, true}, {r, false}}, region,
+               streamId, [=](auto t, char *const *q) {
+                 typedef decltype(t) T;
+                 return CgF<T, false>{q[0], q[1], q[2], q[3], (T)alpha, {}};
+               });
 }
 
-double reduction_end(ExchangeEngine &eng, int dom) {
-  if (dom < 0 || dom >= eng.num_domains())
-    throw std::invalid_argument("reduction_end: no such domain " + std::to_string(dom));
-  ExchangeEngine::ReduceScratch &sc = eng.reduce_scratch(dom, false);
-  if (!sc.pending)
-    throw std::runtime_error("reduction_end: no reduction in flight on domain " +
-                             std::to_string(dom));
-  if (sc.values != 1)
-    throw std::runtime_error("reduction_end: the reduction in flight on domain " +
-                             std::to_string(dom) + " has " + std::to_string(sc.values) +
-                             " values (call reduction_end_n)");
-  sc.pending = false;
-  if (sc.count == 0) return 0.0;
-  STENCIL_HIP(hipSetDevice(eng.domain(dom).gpu()));
-  STENCIL_HIP(hipStreamSynchronize(sc.stream));
-  double sum = 0.0;
-  for (int i = 0; i < sc.count; ++i) sum += sc.host[i]; // index order
-  return sum;
+void cg_update_sum_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p,
+                         int64_t r, const Rect3 &region, int streamId) {
+  check_distinct("cg_update_sum", x, p, r);
+  begin_reduce("cg_update_sum", eng, dom, {{x, false}, {p, false}, {p, true}, {r, false}}, region,
+               streamId, [=](auto t, char *const *q) {
+                 typedef decltype(t) T;
+                 return CgF<T, true>{q[0], q[1], q[2], q[3], (T)alpha, {}};
+               });
 }
 
 void reduction_end_n(ExchangeEngine &eng, int dom, double *out, int n) {
-  if (dom < 0 || dom >= eng.num_domains())
-    throw std::invalid_argument("reduction_end_n: no such domain " + std::to_string(dom));
+  checked_domain("reduction_end", eng, dom);
   if (out == nullptr || n < 1 || n > ExchangeEngine::kReduceValues)
-    throw std::invalid_argument("reduction_end_n: want 1.." +
+    throw std::invalid_argument("reduction_end: want 1.." +
                                 std::to_string(ExchangeEngine::kReduceValues) + " values, got " +
                                 std::to_string(n));
   ExchangeEngine::ReduceScratch &sc = eng.reduce_scratch(dom, false);
   if (!sc.pending)
-    throw std::runtime_error("reduction_end_n: no reduction in flight on domain " +
+    throw std::runtime_error("reduction_end: no reduction in flight on domain " +
                              std::to_string(dom));
-  if (sc.values != n)
-    throw std::runtime_error("reduction_end_n: the reduction in flight on domain " +
+  if (sc.values != n) // it stays in flight
+    throw std::runtime_error("reduction_end: the reduction in flight on domain " +
                              std::to_string(dom) + " has " + std::to_string(sc.values) +
                              " values, not " + std::to_string(n));
   sc.pending = false;
-  sc.values = 1; // what the one-valued ops leave untouched
   for (int v = 0; v < n; ++v) out[v] = 0.0;
   if (sc.count == 0) return;
   STENCIL_HIP(hipSetDevice(eng.domain(dom).gpu()));
@@ -600,64 +514,28 @@ void reduction_end_n(ExchangeEngine &eng, int dom, double *out, int n) {
   }
 }
 
-void field_sum_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
-                     int streamId) {
-  const Launch l = plan_launch("field_sum", eng, dom, {{a, aNext}}, region);
-  ExchangeEngine::ReduceScratch &sc = begin_reduction("field_sum", eng, dom, !l.empty);
-  if (l.empty) return land_empty_n(sc, 1);
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4)
-    VEC_OPS_LAUNCH(float, l, sum_kernel, stream, l.g, (const char *)l.ptr[0], sc.dev);
-  else
-    VEC_OPS_LAUNCH(double, l, sum_kernel, stream, l.g, (const char *)l.ptr[0], sc.dev);
-  land_partials_n(sc, l.blocks, 1, stream);
+double reduction_end(ExchangeEngine &eng, int dom) {
+  double out = 0.0;
+  reduction_end_n(eng, dom, &out, 1);
+  return out;
 }
 
-void field_dot_sums_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b,
-                          bool bNext, const Rect3 &region, int streamId) {
-  const Launch l = plan_launch("field_dot_sums", eng, dom, {{a, aNext}, {b, bNext}}, region);
-  ExchangeEngine::ReduceScratch &sc = begin_reduction("field_dot_sums", eng, dom, !l.empty);
-  if (l.empty) return land_empty_n(sc, 3);
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4)
-    VEC_OPS_LAUNCH(float, l, dot_sums_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], sc.dev);
-  else
-    VEC_OPS_LAUNCH(double, l, dot_sums_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], sc.dev);
-  land_partials_n(sc, l.blocks, 3, stream);
+double field_dot(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                 const Rect3 &region, int streamId) {
+  field_dot_begin(eng, dom, a, aNext, b, bNext, region, streamId);
+  return reduction_end(eng, dom);
 }
 
-void cg_update_sum_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p,
-                         int64_t r, const Rect3 &region, int streamId) {
-  // operands: curr[x], curr[p], next[p] (= A p), curr[r]
-  const Launch l = plan_launch("cg_update_sum", eng, dom,
-                               {{x, false}, {p, false}, {p, true}, {r, false}}, region);
-  if (x == p || x == r || p == r)
-    throw std::invalid_argument("cg_update_sum: x, p and r must be distinct quantities");
-  ExchangeEngine::ReduceScratch &sc = begin_reduction("cg_update_sum", eng, dom, !l.empty);
-  if (l.empty) return land_empty_n(sc, 2);
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4) {
-    const float al = (float)alpha; // the one rounding to the quantity's type
-    VEC_OPS_LAUNCH(float, l, cg_update_sum_kernel, stream, l.g, l.ptr[0], (const char *)l.ptr[1],
-                   (const char *)l.ptr[2], l.ptr[3], al, sc.dev);
-  } else {
-    VEC_OPS_LAUNCH(double, l, cg_update_sum_kernel, stream, l.g, l.ptr[0],
-                   (const char *)l.ptr[1], (const char *)l.ptr[2], l.ptr[3], alpha, sc.dev);
-  }
-  land_partials_n(sc, l.blocks, 2, stream);
+double cg_update(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
+                 const Rect3 &region, int streamId) {
+  cg_update_begin(eng, dom, alpha, x, p, r, region, streamId);
+  return reduction_end(eng, dom);
 }
 
 double field_sum(ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
                  int streamId) {
   field_sum_begin(eng, dom, a, aNext, region, streamId);
-  double out[1];
-  reduction_end_n(eng, dom, out, 1);
-  return out[0];
+  return reduction_end(eng, dom);
 }
 
 std::array<double, 3> field_dot_sums(ExchangeEngine &eng, int dom, int64_t a, bool aNext,
@@ -676,92 +554,46 @@ std::array<double, 2> cg_update_sum(ExchangeEngine &eng, int dom, double alpha, 
   return out;
 }
 
-void field_axpbyc(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
-                  int64_t y, bool yNext, double c, int64_t out, bool outNext,
-                  const Rect3 &region, int streamId) {
-  const Launch l =
-      plan_launch("field_axpbyc", eng, dom, {{x, xNext}, {y, yNext}, {out, outNext}}, region);
-  if (l.empty) return;
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4) {
-    const float al = (float)alpha, be = (float)beta, cc = (float)c; // rounded once
-    VEC_OPS_LAUNCH(float, l, axpbyc_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], l.ptr[2], al, be, cc);
-  } else {
-    VEC_OPS_LAUNCH(double, l, axpbyc_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], l.ptr[2], alpha, beta, c);
-  }
-}
-
-double field_dot(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
-                 const Rect3 &region, int streamId) {
-  field_dot_begin(eng, dom, a, aNext, b, bNext, region, streamId);
-  return reduction_end(eng, dom);
-}
-
-double cg_update(ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
-                 const Rect3 &region, int streamId) {
-  cg_update_begin(eng, dom, alpha, x, p, r, region, streamId);
-  return reduction_end(eng, dom);
-}
-
 void field_axpby(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
                  int64_t y, bool yNext, int64_t out, bool outNext, const Rect3 &region,
                  int streamId) {
-  const Launch l =
-      plan_launch("field_axpby", eng, dom, {{x, xNext}, {y, yNext}, {out, outNext}}, region);
-  if (l.empty) return;
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4) {
-    const float al = (float)alpha, be = (float)beta; // the one rounding to the quantity's type
-    VEC_OPS_LAUNCH(float, l, axpby_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], l.ptr[2], al, be);
-  } else {
-    VEC_OPS_LAUNCH(double, l, axpby_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], l.ptr[2], alpha, beta);
-  }
+  run_field("field_axpby", eng, dom, {{x, xNext}, {y, yNext}, {out, outNext}}, region, streamId,
+            [=](auto t, char *const *p) {
+              typedef decltype(t) T;
+              return AxpbyF<T>{p[0], p[1], p[2], (T)alpha, (T)beta};
+            });
+}
+
+void field_axpbyc(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
+                  int64_t y, bool yNext, double c, int64_t out, bool outNext,
+                  const Rect3 &region, int streamId) {
+  run_field("field_axpbyc", eng, dom, {{x, xNext}, {y, yNext}, {out, outNext}}, region, streamId,
+            [=](auto t, char *const *p) {
+              typedef decltype(t) T;
+              return AxpbycF<T>{p[0], p[1], p[2], (T)alpha, (T)beta, (T)c};
+            });
 }
 
 void field_axpbypcz(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
                     double beta, int64_t y, bool yNext, double gamma, int64_t z, bool zNext,
                     int64_t out, bool outNext, const Rect3 &region, int streamId) {
-  const Launch l = plan_launch("field_axpbypcz", eng, dom,
-                               {{x, xNext}, {y, yNext}, {z, zNext}, {out, outNext}}, region);
-  if (l.empty) return;
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4) {
-    const float al = (float)alpha, be = (float)beta, ga = (float)gamma; // rounded once
-    VEC_OPS_LAUNCH(float, l, axpbypcz_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], (const char *)l.ptr[2], l.ptr[3], al, be, ga);
-  } else {
-    VEC_OPS_LAUNCH(double, l, axpbypcz_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], (const char *)l.ptr[2], l.ptr[3], alpha, beta, gamma);
-  }
+  run_field("field_axpbypcz", eng, dom, {{x, xNext}, {y, yNext}, {z, zNext}, {out, outNext}},
+            region, streamId, [=](auto t, char *const *p) {
+              typedef decltype(t) T;
+              return AxpbypczF<T>{p[0], p[1], p[2], p[3], (T)alpha, (T)beta, (T)gamma};
+            });
 }
 
 void field_scaled_update(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
                          int64_t d, bool dNext, double beta, int64_t y, bool yNext, double gamma,
                          int64_t z, bool zNext, int64_t out, bool outNext, const Rect3 &region,
                          int streamId) {
-  const Launch l =
-      plan_launch("field_scaled_update", eng, dom,
-                  {{x, xNext}, {d, dNext}, {y, yNext}, {z, zNext}, {out, outNext}}, region);
-  if (l.empty) return;
-  STENCIL_HIP(hipSetDevice(l.d->gpu()));
-  hipStream_t stream = eng.compute_stream(dom, streamId);
-  if (l.es == 4) {
-    const float al = (float)alpha, be = (float)beta, ga = (float)gamma; // rounded once
-    VEC_OPS_LAUNCH(float, l, scaled_update_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], (const char *)l.ptr[2], (const char *)l.ptr[3],
-                   l.ptr[4], al, be, ga);
-  } else {
-    VEC_OPS_LAUNCH(double, l, scaled_update_kernel, stream, l.g, (const char *)l.ptr[0],
-                   (const char *)l.ptr[1], (const char *)l.ptr[2], (const char *)l.ptr[3],
-                   l.ptr[4], alpha, beta, gamma);
-  }
+  run_field("field_scaled_update", eng, dom,
+            {{x, xNext}, {d, dNext}, {y, yNext}, {z, zNext}, {out, outNext}}, region, streamId,
+            [=](auto t, char *const *p) {
+              typedef decltype(t) T;
+              return ScaledF<T>{p[0], p[1], p[2], p[3], p[4], (T)alpha, (T)beta, (T)gamma};
+            });
 }
 
 } // namespace stencil_amd

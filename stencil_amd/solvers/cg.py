@@ -323,17 +323,13 @@ class ConjugateGradient:
         constant b gives "zero_rhs", b is never written, and x is
         projected (x -= mean(x)) on every exit that returns a solution."""
         self.corrections = 0
-        if self.nullspace is None:
-            res = self._solve(tol, max_iter, x0_zero, overlap)
-            if self.correction is None or not res.converged or res.reason == "zero_rhs":
-                return res
-            return self._refine(res, tol, max_iter, overlap)
-        res = self._solve_projected(tol, max_iter, x0_zero, overlap)
+        res = self._solve(tol, max_iter, x0_zero, overlap)
         if res.reason == "zero_rhs":
             return res
         if self.correction is not None and res.converged:
             res = self._refine(res, tol, max_iter, overlap)
-        self._project(self.x)
+        if self.nullspace is not None:
+            self._project(self.x)
         return res
 
     def _project(self, h: DataHandle):
@@ -369,19 +365,9 @@ class ConjugateGradient:
             dd.axpby(0.0, r, 0.0, r, out=d)
             dd.axpby(1.0, r, 0.0, r, out=p)
             dd.backend.sync_compute()
-            self.x = d  # the loops below update self.x
+            self.x = d  # _iterate updates self.x
             try:
-                left = max_iter - its
-                if ns and self.M is not None:
-                    inner = self._iterate_preconditioned_projected(limit, bb, residuals, left,
-                                                                   overlap)
-                elif ns:
-                    inner = self._iterate_plain_projected(rr, limit, bb, residuals, left,
-                                                          overlap)
-                elif self.M is not None:
-                    inner = self._iterate_preconditioned(limit, bb, residuals, left, overlap)
-                else:
-                    inner = self._iterate_plain(rr, limit, bb, residuals, left, overlap)
+                inner = self._iterate(rr, limit, bb, residuals, max_iter - its, overlap)
             finally:
                 self.x = x
             dd.axpby(1.0, x, 1.0, d, out=x)
@@ -391,140 +377,44 @@ class ConjugateGradient:
                 return CGResult(False, its, residuals, inner.reason)
 
     def _solve(self, tol, max_iter, x0_zero, overlap) -> CGResult:
+        """the set-up, then _iterate. nullspace="constant": for A x = P b,
+        with r = P b first and bb = r . r of that r, the norm every
+        residual is relative to."""
         dd, x, b, r, p = self.dd, self.x, self.b, self.r, self.p
+        ns = self.nullspace is not None
         self.phase_times = {k: 0.0 for k in self.phase_times}
         if not x0_zero and self.group_x is None:
             raise ValueError("solve(x0_zero=False) needs group_x, the exchange group of x")
-        bb = dd.dot(b)
-        if not math.isfinite(bb):
-            return CGResult(False, 0, [float("nan")], "breakdown")
-        if bb == 0.0:
-            dd.axpby(0.0, b, 0.0, b, out=x)  # b is all zeros: so is x
-            dd.backend.sync_compute()
-            return CGResult(True, 0, [0.0], "zero_rhs")
-        if x0_zero:
-            dd.axpby(0.0, b, 0.0, b, out=x)
-            dd.axpby(1.0, b, 0.0, b, out=r)
-        else:
-            self._apply(x, self.group_x, overlap)
-            dd.axpby(1.0, b, -1.0, Next(x), out=r)
-        dd.axpby(1.0, r, 0.0, r, out=p)
-        rr = dd.dot(r)
-        dd.backend.sync_compute()  # the exchange reads p on other streams
-        residuals = [math.sqrt(rr / bb)] if math.isfinite(rr) else [float("nan")]
-        if not math.isfinite(rr):
-            return CGResult(False, 0, residuals, "breakdown")
-        limit = tol * tol * bb
-        if rr <= limit:
-            return CGResult(True, 0, residuals, "converged")
-        if self.M is not None:
-            return self._iterate_preconditioned(limit, bb, residuals, max_iter, overlap)
-        return self._iterate_plain(rr, limit, bb, residuals, max_iter, overlap)
-
-    def _iterate_plain(self, rr, limit, bb, residuals, max_iter, overlap) -> CGResult:
-        """the plain loop from p = r, rr = r . r; updates self.x"""
-        dd, x, r, p = self.dd, self.x, self.r, self.p
-        for it in range(1, max_iter + 1):
-            t0 = time.perf_counter()
-            self._apply(p, self.group_p, overlap)
-            t1 = time.perf_counter()
-            pap = dd.dot(p, Next(p))
-            t2 = time.perf_counter()
-            self.phase_times["operator"] += t1 - t0
-            self.phase_times["dot"] += t2 - t1
-            if not (math.isfinite(pap) and pap > 0.0):
-                return CGResult(False, it - 1, residuals, "breakdown")
-            alpha = rr / pap
-            rr_new = dd.cg_update(alpha, x, p, r)
-            if not math.isfinite(rr_new):
-                self.phase_times["update"] += time.perf_counter() - t2
-                return CGResult(False, it, residuals + [float("nan")], "breakdown")
-            residuals.append(math.sqrt(rr_new / bb))
-            if rr_new <= limit:
-                self.phase_times["update"] += time.perf_counter() - t2
-                return CGResult(True, it, residuals, "converged")
-            dd.axpby(1.0, r, rr_new / rr, p, out=p)
-            dd.backend.sync_compute()  # before the next exchange reads p
-            rr = rr_new
-            self.phase_times["update"] += time.perf_counter() - t2
-        return CGResult(False, max_iter, residuals, "max_iter")
-
-    def _precondition(self) -> float:
-        """z = M r; returns r . z"""
-        t0 = time.perf_counter()
-        self.M.apply(self.r, self.z)
-        rz = self.dd.dot(self.r, self.z)
-        self.phase_times["precond"] += time.perf_counter() - t0
-        return rz
-
-    def _iterate_preconditioned(self, limit, bb, residuals, max_iter, overlap) -> CGResult:
-        """the loop of solve() with z = M r in the place of r: p = z,
-        alpha = r.z / p.Ap, beta = r.z' / r.z. The stopping test and
-        `residuals` stay on r . r, which cg_update still returns. A
-        non-finite or non-positive r . z (M not positive definite) is a
-        breakdown."""
-        dd, x, r, p, z = self.dd, self.x, self.r, self.p, self.z
-        rz = self._precondition()
-        if not (math.isfinite(rz) and rz > 0.0):
-            return CGResult(False, 0, residuals, "breakdown")
-        dd.axpby(1.0, z, 0.0, z, out=p)
-        dd.backend.sync_compute()
-        for it in range(1, max_iter + 1):
-            t0 = time.perf_counter()
-            self._apply(p, self.group_p, overlap)
-            t1 = time.perf_counter()
-            pap = dd.dot(p, Next(p))
-            t2 = time.perf_counter()
-            self.phase_times["operator"] += t1 - t0
-            self.phase_times["dot"] += t2 - t1
-            if not (math.isfinite(pap) and pap > 0.0):
-                return CGResult(False, it - 1, residuals, "breakdown")
-            rr_new = dd.cg_update(rz / pap, x, p, r)
-            self.phase_times["update"] += time.perf_counter() - t2
-            if not math.isfinite(rr_new):
-                return CGResult(False, it, residuals + [float("nan")], "breakdown")
-            residuals.append(math.sqrt(rr_new / bb))
-            if rr_new <= limit:
-                return CGResult(True, it, residuals, "converged")
-            rz_new = self._precondition()
-            if not (math.isfinite(rz_new) and rz_new > 0.0):
-                return CGResult(False, it, residuals, "breakdown")
-            t3 = time.perf_counter()
-            dd.axpby(1.0, z, rz_new / rz, p, out=p)
-            dd.backend.sync_compute()  # before the next exchange reads p
-            rz = rz_new
-            self.phase_times["update"] += time.perf_counter() - t3
-        return CGResult(False, max_iter, residuals, "max_iter")
-
-    # ---- nullspace="constant": the loops above with P v = v - mean(v) ----
-    def _solve_projected(self, tol, max_iter, x0_zero, overlap) -> CGResult:
-        """_solve for A x = P b. r = P b first, and bb = r . r of that r:
-        the norm every residual is relative to."""
-        dd, x, b, r, p = self.dd, self.x, self.b, self.r, self.p
-        self.phase_times = {k: 0.0 for k in self.phase_times}
-        if not x0_zero and self.group_x is None:
-            raise ValueError("solve(x0_zero=False) needs group_x, the exchange group of x")
-        sb = dd.sum(b)
-        if not math.isfinite(sb):
-            return CGResult(False, 0, [float("nan")], "breakdown")
-        dd.axpbyc(1.0, b, 0.0, b, -sb / self._cells, out=r)
-        bb = dd.dot(r)
+        rhs = b
+        if ns:
+            sb = dd.sum(b)
+            if not math.isfinite(sb):
+                return CGResult(False, 0, [float("nan")], "breakdown")
+            dd.axpbyc(1.0, b, 0.0, b, -sb / self._cells, out=r)
+            rhs = r
+        bb = dd.dot(rhs)
         if not math.isfinite(bb):
             return CGResult(False, 0, [float("nan")], "breakdown")
         self._bb = bb
         if bb == 0.0:
-            dd.axpby(0.0, r, 0.0, r, out=x)  # P b is all zeros: so is x
+            dd.axpby(0.0, rhs, 0.0, rhs, out=x)  # the right-hand side is all zeros: so is x
             dd.backend.sync_compute()
             return CGResult(True, 0, [0.0], "zero_rhs")
         if x0_zero:
-            dd.axpby(0.0, r, 0.0, r, out=x)
-            rr = bb
+            dd.axpby(0.0, rhs, 0.0, rhs, out=x)
+            if ns:
+                rr = bb
+            else:
+                dd.axpby(1.0, b, 0.0, b, out=r)
         else:
             self._apply(x, self.group_x, overlap)
-            dd.axpby(1.0, r, -1.0, Next(x), out=r)
-            self._project(r)
-            rr = dd.dot(r)
+            dd.axpby(1.0, rhs, -1.0, Next(x), out=r)
+            if ns:
+                self._project(r)
+                rr = dd.dot(r)
         dd.axpby(1.0, r, 0.0, r, out=p)
+        if not ns:
+            rr = dd.dot(r)
         dd.backend.sync_compute()  # the exchange reads p on other streams
         residuals = [math.sqrt(rr / bb)] if math.isfinite(rr) else [float("nan")]
         if not math.isfinite(rr):
@@ -532,63 +422,56 @@ class ConjugateGradient:
         limit = tol * tol * bb
         if rr <= limit:
             return CGResult(True, 0, residuals, "converged")
-        if self.M is not None:
-            return self._iterate_preconditioned_projected(limit, bb, residuals, max_iter, overlap)
-        return self._iterate_plain_projected(rr, limit, bb, residuals, max_iter, overlap)
+        return self._iterate(rr, limit, bb, residuals, max_iter, overlap)
 
-    def _iterate_plain_projected(self, rr, limit, bb, residuals, max_iter, overlap) -> CGResult:
-        """_iterate_plain from a mean-free p = r. cg_update_sum returns
-        sum r next to r . r: rr_p = (P r) . (P r) drives the stopping test
-        and beta, and p = P r + beta p is one axpbyc. No pass more than
-        the plain loop."""
-        dd, x, r, p, n = self.dd, self.x, self.r, self.p, self._cells
-        for it in range(1, max_iter + 1):
-            t0 = time.perf_counter()
-            self._apply(p, self.group_p, overlap)
-            t1 = time.perf_counter()
-            pap = dd.dot(p, Next(p))
-            t2 = time.perf_counter()
-            self.phase_times["operator"] += t1 - t0
-            self.phase_times["dot"] += t2 - t1
-            if not (math.isfinite(pap) and pap > 0.0):
-                return CGResult(False, it - 1, residuals, "breakdown")
-            alpha = rr / pap
-            rr_raw, sr = dd.cg_update_sum(alpha, x, p, r)
-            rr_new = max(rr_raw - sr * sr / n, 0.0)
-            if not math.isfinite(rr_new):
-                self.phase_times["update"] += time.perf_counter() - t2
-                return CGResult(False, it, residuals + [float("nan")], "breakdown")
-            residuals.append(math.sqrt(rr_new / bb))
-            if rr_new <= limit:
-                self.phase_times["update"] += time.perf_counter() - t2
-                return CGResult(True, it, residuals, "converged")
-            dd.axpbyc(1.0, r, rr_new / rr, p, -sr / n, out=p)
-            dd.backend.sync_compute()  # before the next exchange reads p
-            rr = rr_new
-            self.phase_times["update"] += time.perf_counter() - t2
-        return CGResult(False, max_iter, residuals, "max_iter")
-
-    def _precondition_projected(self):
-        """z = M r; returns ((P r) . (P z), sum z) from one dot_sums pass"""
+    def _precondition(self):
+        """z = M r; returns (r . z, None), or with nullspace="constant"
+        ((P r) . (P z), -sum z / N) from one dot_sums pass"""
         t0 = time.perf_counter()
         self.M.apply(self.r, self.z)
-        rz, sr, sz = self.dd.dot_sums(self.r, self.z)
+        if self.nullspace is None:
+            rz, shift = self.dd.dot(self.r, self.z), None
+        else:
+            rz, sr, sz = self.dd.dot_sums(self.r, self.z)
+            rz, shift = rz - sr * sz / self._cells, -sz / self._cells
         self.phase_times["precond"] += time.perf_counter() - t0
-        return rz - sr * sz / self._cells, sz
+        return rz, shift
 
-    def _iterate_preconditioned_projected(self, limit, bb, residuals, max_iter,
-                                          overlap) -> CGResult:
-        """_iterate_preconditioned with P z in the place of z: M r has a
-        constant component even for a mean-free r (a smoother that scales
-        per cell), which must reach neither p nor x. The stopping test
-        stays on cg_update's r . r; the breakdown rules apply to the
-        projected r . z."""
-        dd, x, r, p, z, n = self.dd, self.x, self.r, self.p, self.z, self._cells
-        rz, sz = self._precondition_projected()
-        if not (math.isfinite(rz) and rz > 0.0):
-            return CGResult(False, 0, residuals, "breakdown")
-        dd.axpbyc(1.0, z, 0.0, z, -sz / n, out=p)
-        dd.backend.sync_compute()
+    def _set_p(self, v: DataHandle, beta: float, y: DataHandle, shift: Optional[float]):
+        """p = v + beta y, plus the constant `shift` unless it is None"""
+        if shift is None:
+            self.dd.axpby(1.0, v, beta, y, out=self.p)
+        else:
+            self.dd.axpbyc(1.0, v, beta, y, shift, out=self.p)
+        self.dd.backend.sync_compute()  # before the next exchange reads p
+
+    def _iterate(self, rho, limit, bb, residuals, max_iter, overlap) -> CGResult:
+        """the loop from p = r and rho = r . r; updates self.x.
+
+        With a preconditioner z = M r stands in the place of r: p = z,
+        rho = r . z, alpha = rho / p.Ap, beta = rho' / rho. The stopping
+        test and `residuals` stay on r . r, which cg_update still returns.
+        A non-finite or non-positive r . z (M not positive definite) is a
+        breakdown.
+
+        With nullspace="constant" p starts mean-free and stays so at no
+        pass more. Plain: cg_update_sum returns sum r next to r . r;
+        (P r) . (P r) drives the stopping test and beta, and
+        p = P r + beta p is one axpbyc. Preconditioned: P z stands in the
+        place of z, since M r has a constant component even for a
+        mean-free r (a smoother that scales per cell) which must reach
+        neither p nor x; the stopping test stays on cg_update's r . r and
+        the breakdown rules apply to the projected r . z."""
+        dd, x, r, p, n = self.dd, self.x, self.r, self.p, self._cells
+        pre = self.M is not None
+        summed = self.nullspace is not None and not pre  # cg_update_sum in the place of cg_update
+        v, shift = r, None  # what p is built from: r or z, and the constant that projects it
+        if pre:
+            v = self.z
+            rho, shift = self._precondition()
+            if not (math.isfinite(rho) and rho > 0.0):
+                return CGResult(False, 0, residuals, "breakdown")
+            self._set_p(v, 0.0, v, shift)
         for it in range(1, max_iter + 1):
             t0 = time.perf_counter()
             self._apply(p, self.group_p, overlap)
@@ -599,19 +482,24 @@ class ConjugateGradient:
             self.phase_times["dot"] += t2 - t1
             if not (math.isfinite(pap) and pap > 0.0):
                 return CGResult(False, it - 1, residuals, "breakdown")
-            rr_new = dd.cg_update(rz / pap, x, p, r)
+            if summed:
+                rr_raw, sr = dd.cg_update_sum(rho / pap, x, p, r)
+                rr_new, shift = max(rr_raw - sr * sr / n, 0.0), -sr / n
+            else:
+                rr_new = dd.cg_update(rho / pap, x, p, r)
             self.phase_times["update"] += time.perf_counter() - t2
             if not math.isfinite(rr_new):
                 return CGResult(False, it, residuals + [float("nan")], "breakdown")
             residuals.append(math.sqrt(rr_new / bb))
             if rr_new <= limit:
                 return CGResult(True, it, residuals, "converged")
-            rz_new, sz = self._precondition_projected()
-            if not (math.isfinite(rz_new) and rz_new > 0.0):
-                return CGResult(False, it, residuals, "breakdown")
+            rho_new = rr_new
+            if pre:
+                rho_new, shift = self._precondition()
+                if not (math.isfinite(rho_new) and rho_new > 0.0):
+                    return CGResult(False, it, residuals, "breakdown")
             t3 = time.perf_counter()
-            dd.axpbyc(1.0, z, rz_new / rz, p, -sz / n, out=p)
-            dd.backend.sync_compute()  # before the next exchange reads p
-            rz = rz_new
+            self._set_p(v, rho_new / rho, p, shift)
+            rho = rho_new
             self.phase_times["update"] += time.perf_counter() - t3
         return CGResult(False, max_iter, residuals, "max_iter")
