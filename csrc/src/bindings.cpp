@@ -16,6 +16,7 @@
 #include "stencil_amd/domain.hpp"
 #include "stencil_amd/engine.hpp"
 #include "stencil_amd/hip_check.hpp"
+#include "stencil_amd/jacobi_fuse2_map.hpp"
 #include "stencil_amd/ops.hpp"
 #include "stencil_amd/partition.hpp"
 #include "stencil_amd/placement.hpp"
@@ -615,6 +616,24 @@ PYBIND11_MODULE(_C, m) {
   m.def("jacobi_graph_sync", [](JacobiStepGraph &g) { g.sync(); });
   m.def("jacobi_graph_is_wrap", [](JacobiStepGraph &g) { return g.is_wrap(); });
   m.def("jacobi_graph_is_fused2", [](JacobiStepGraph &g) { return g.is_fused2(); });
+  // test only: the byte offsets (from cell 0 of row 0 of a plane) that the 64
+  // lanes of one wave of jacobi_kernel_fuse2 hold for its gathered load. The
+  // wave is row `yb` (unwrapped, -1 .. ) of the tile that starts at vector
+  // `ub` of a row of `body4` vectors whose true cells are [under, last].
+  m.def(
+      "jacobi_fuse2_gather_offsets",
+      [](int32_t ub, int32_t body4, int32_t under, int32_t last, int32_t yb, int32_t extY,
+         uint32_t pitch) {
+        const int32_t eL = f2_edge_left(ub, last), eR = f2_edge_right(ub, body4, under);
+        const int32_t yo = f2_pmod(yb, extY), ym = f2_pmod(yb - 1, extY),
+                      yp = f2_pmod(yb + 1, extY);
+        std::vector<uint32_t> out(64);
+        for (int lane = 0; lane < 64; ++lane)
+          out[lane] = f2_gather_offset(lane, eL, eR, under, last, yo, ym, yp, pitch);
+        return out;
+      },
+      py::arg("ub"), py::arg("body4"), py::arg("under"), py::arg("last"), py::arg("yb"),
+      py::arg("ext_y"), py::arg("pitch"));
   // test only: the device division helper (device_util.hpp div6) applied to
   // every element of a float32 array, on the current device
   m.def(

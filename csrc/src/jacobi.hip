@@ -34,8 +34,11 @@
 //     div6 of device_util.hpp, bit for bit the IEEE quotient; the
 //     single-step kernels keep `/ 6.0f` (no measurable difference there:
 //     they wait on memory at 8 waves/SIMD). 0.531 vs 0.722 ms/step, median
-//     of 5 alternating runs (profiles/README.md). STENCIL_JAC_FUSE2=0 forces
-//     single-step replays.
+//     of 5 alternating runs (profiles/README.md). Its x neighbours come from
+//     the neighbouring lanes' registers and everything from outside a tile
+//     from one gathered load per wave and plane, on scalar bases with 32-bit
+//     lane offsets: 78 instead of 122 VGPRs, a third block per CU, 0.393 vs
+//     0.531 ms/step. STENCIL_JAC_FUSE2=0 forces single-step replays.
 // Hot/cold sphere sources match the reference's behavior (truncated-int
 // sqrtf distance, HOT=1/COLD=0 fixed cells) so results are comparable.
 #include <hip/hip_runtime.h>
@@ -54,6 +57,7 @@
 #include "stencil_amd/engine.hpp"
 #include "stencil_amd/field_op.hpp"
 #include "stencil_amd/hip_check.hpp"
+#include "stencil_amd/jacobi_fuse2_map.hpp"
 #include "stencil_amd/ops.hpp"
 
 namespace stencil_amd {
@@ -413,9 +417,47 @@ jacobi_kernel_v4_lds(std::conditional_t<WRAP, JacobiWrapParams, JacobiParams> p)
   }
 }
 
-__device__ __forceinline__ int32_t pmod(int32_t a, int32_t n) {
-  const int32_t m = a % n;
-  return m < 0 ? m + n : m;
+// Lane shifts of one VGPR by data-parallel-primitive moves (no LDS, no
+// memory). Every lane of the wave must be active where they are used.
+//   lane_below: lane i gets v of lane i-1 of the wave, lane 0 gets `first`
+//   lane_above: lane i gets v of lane i+1 of the wave, lane 63 keeps its own
+//   row_above<N>: lane i gets lane i+N of its 16-lane row (0 past the row)
+__device__ __forceinline__ float lane_below(float v, float first) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v),
+                                                    0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float lane_above(float v) {
+  const int i = __float_as_int(v);
+  return __int_as_float(__builtin_amdgcn_update_dpp(i, i, 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+}
+template <int N> __device__ __forceinline__ float row_above(float v) {
+  static_assert(N >= 1 && N <= 15, "row shift");
+  return __int_as_float(
+      __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + N /* row_shl:N */, 0xf, 0xf, true));
+}
+// A wave-uniform address as a scalar-register base in the GLOBAL address
+// space: the loads and the store below then take the form scalar base +
+// 32-bit lane offset. (Through a generic pointer they would become flat
+// instructions, and without the pin the compiler folds the lane offset into a
+// per-lane 64-bit pointer and multiplies per load.)
+typedef float vfloat4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) char gchar;
+__device__ __forceinline__ gchar *global_base(const void *p) {
+  const uint64_t v = (uint64_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (gchar *)(((uint64_t)hi << 32) | lo);
+}
+// A loop-invariant 32-bit lane offset, made opaque at its use: the zero
+// extension then stays next to the access, where instruction selection folds
+// it into the scalar-base form; hoisted out of the loop it becomes a 64-bit
+// register pair and a 64-bit vector add per access.
+__device__ __forceinline__ uint32_t lane_offset(uint32_t o) {
+  asm volatile("" : "+v"(o));
+  return o;
+}
+__device__ __forceinline__ float lane_value(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
 // Two time steps in one pass over memory, for the same launch the WRAP
@@ -424,11 +466,13 @@ __device__ __forceinline__ int32_t pmod(int32_t a, int32_t n) {
 // values exist only in LDS and registers, so the field makes one trip
 // through HBM per TWO steps.
 //
-// Tiling: a 64 x NY block marches z. Lane (tx, ry) owns the float4 at
-// vector blockIdx.x*64+tx of row blockIdx.y*(NY-2)-1+ry. Every lane
-// computes stage 1 (time t+1) of its vector, the inner NY-2 rows also
-// compute stage 2 (time t+2) and store it: 2 of NY rows are redundant
-// stage-1 work (25% at NY = 8), and there is NO x halo lane.
+// Tiling: a 64 x NY block marches z. A wave is one row of the block: lane
+// (tx, ry) owns the float4 at vector blockIdx.x*64+tx of row
+// blockIdx.y*(NY-2)-1+ry, and everything that depends on the row alone (ry
+// is read through readfirstlane) is scalar. Every lane computes stage 1
+// (time t+1) of its vector, the inner NY-2 rows also compute stage 2 (time
+// t+2) and store it: 2 of NY rows are redundant stage-1 work (25% at NY =
+// 8), and there is NO x halo lane.
 //   y: stage 1 reads the t rows above and below from tT (NY+2 rows: the
 //      block's own, plus one halo row staged by ry==0 and one by ry==NY-1),
 //      stage 2 reads the t+1 rows above and below from tS (NY rows). Both
@@ -439,17 +483,27 @@ __device__ __forceinline__ int32_t pmod(int32_t a, int32_t n) {
 //      plane z-1. A block owns a chunk of planes [lz0, zEnd) and runs the
 //      loop over lz0-1 .. zEnd: 2 extra stage-1 planes and 4 extra t planes
 //      per chunk. Vector loads (own vector and halo row) run two planes
-//      ahead of their use, scalar loads one (see the loop).
-//   x: inside a vector the neighbours are components; across vectors stage
-//      1 loads the two t scalars from global memory as the WRAP kernel does
-//      and stage 2 reads the t+1 scalar from the neighbouring lane's tS
-//      entry. At a tile's two x edges that neighbour belongs to another
-//      block (or, at a row's end, is the periodic image of the row's other
-//      end), so lanes 0 and 1 of each wave (= row) compute that single t+1
-//      cell themselves, from six t scalars, and hand it to the edge lanes:
-//      one two-lane divergent section per wave and plane, instead of two
-//      halo lanes per row that would push 188 vectors into a fourth,
-//      nearly empty block column.
+//      ahead of their use, the gathered load one (see the loop).
+//   x: inside a vector the neighbours are components; across vectors they
+//      are the neighbouring LANES' registers at both stages (cc / sc of lane
+//      tx-1 and tx+1, one lane shift each): no load and no LDS read. Only
+//      the two lanes at a tile's x edges need a value from outside the wave.
+//      There the neighbour belongs to another block (or, at a row's end, is
+//      the periodic image of the row's other end): edge cells eL and eR. At
+//      stage 1 the edge lanes take the t values of eL / eR; at stage 2 they
+//      need the t+1 values, which lanes 0 and 1 of each wave compute
+//      themselves from the six t neighbours of eL / eR. All of that arrives
+//      by ONE gathered global_load_dword per wave and plane (ten lanes
+//      useful, table in jacobi_fuse2_map.hpp): the t values of e and of its
+//      four x / y neighbours in the plane after stage 1's. The z neighbours
+//      of e are e itself one plane later and earlier, so the last three
+//      gathered registers are kept (g1, g2, g3) and lanes 0 / 1 sum
+//      their six operands with row shifts, in the order every other cell
+//      is summed in.
+// Addresses: every load and the store is a wave-uniform 64-bit base (buffer
+// + row + plane, scalar unit) plus a 32-bit lane offset that never changes
+// (the global saddr + voffset form); the gathered offset is below the plane
+// stride, which jacobi_fuse2_eligible bounds to 31 bits.
 // Periodic wrap is a true modulo on every axis (rows and planes by index,
 // x by the row's true first/last cell), so extents down to x=8, y=1, z=1
 // are exact; the sphere override runs after each stage at the WRAPPED
@@ -457,27 +511,44 @@ __device__ __forceinline__ int32_t pmod(int32_t a, int32_t n) {
 // row's first/last vector hold garbage at both stages and are stored, like
 // the WRAP kernel's, only into cells row_extension mode 1 permits; no true
 // cell ever reads one (the wl*/wr* selects replace exactly those
-// neighbours). No halo cell is read. No lane returns before a barrier:
-// out-of-range lanes clamp or wrap their coordinates and skip the store.
+// neighbours, and a lane shift across vectors only ever delivers component
+// 3 of a row's first or component 0 of its last vector, both true cells).
+// Lanes past a row's last vector (tx > rl) hold garbage that no other lane
+// reads: lane rl takes its right neighbours from the gathered values. No
+// halo cell is read. No lane returns before a barrier: out-of-range lanes
+// clamp or wrap their coordinates and skip the store.
 // The division is div6 (device_util.hpp): 3 instructions per value instead
 // of the IEEE expansion's 11, the same bits.
 // gfx950 resource usage (-Rpass-analysis=kernel-resource-usage), NY = 8:
-//   122 VGPRs, 82 SGPRs, 0 scratch, 4 waves/SIMD, 36864 B LDS: two blocks
-//   (16 waves) per CU, bound by the VGPRs.
+//   78 VGPRs, 78 SGPRs, 0 scratch, 6 waves/SIMD, 36864 B LDS: three blocks
+//   (24 waves) per CU, bound by the VGPRs (80 is the most for 6 waves/SIMD).
+//   Before the lane shifts and the gathered load: 122 VGPRs, 82 SGPRs, two
+//   blocks per CU.
+// The loop body, two planes, every block of it counted (the IEEE-division
+// fallback of div6 and the sphere tests included), before -> now:
+//   global_load_dword 16 -> 2, global_load_dwordx4 4 -> 4, stores 2 -> 2,
+//   ds_read 12 -> 8 (b128 only), ds_write_b128 6 -> 6, ds_bpermute 2 -> 0,
+//   v_mad_u64_u32 12 -> 0, v_lshl_add_u64 14 -> 0, v_mov_b64 38 -> 26,
+//   v_mov_b32 34 -> 72 (the lane shifts' operands and results among them),
+//   v_mov_b32_dpp 0 -> 18, v_readlane_b32 0 -> 6. Every global access has the
+//   saddr + voffset form. The load queue is still drained once per two
+//   planes at the loop latch, where the register slots are copied.
 // Measured at 750^3 (profiles/README.md, "Fused two-step jacobi graph").
 template <int NY>
 __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams p) {
   __shared__ float4 tT[2][NY + 2][64];
   __shared__ float4 tS[2][NY][64];
   const int32_t tx = threadIdx.x;
-  const int32_t ry = threadIdx.y;
+  // blockDim.x is the wave size, so threadIdx.y is the same in all 64 lanes
+  const int32_t ry = __builtin_amdgcn_readfirstlane((int32_t)threadIdx.y);
   const int32_t body4 = p.extX / 4; // vecAll: extX % 4 == 0
   const int32_t ub = blockIdx.x * 64;
   const int32_t u0 = ub + tx;
   const int32_t u = min(u0, body4 - 1);
-  // rows: unwrapped yb, and the wrapped rows the lane touches
+  // rows: unwrapped yb, and the wrapped rows the wave touches
   const int32_t yb = (int32_t)blockIdx.y * (NY - 2) - 1 + ry;
-  const int32_t yo = pmod(yb, p.extY), ym = pmod(yb - 1, p.extY), yp = pmod(yb + 1, p.extY);
+  const int32_t yo = f2_pmod(yb, p.extY), ym = f2_pmod(yb - 1, p.extY),
+                yp = f2_pmod(yb + 1, p.extY);
   const bool valid = u0 < body4 && ry >= 1 && ry <= NY - 2 && yb < p.extY;
   // planes: the chunk is derived from the grid, so the launcher alone
   // decides its length
@@ -485,18 +556,18 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
   const int32_t lz0 = blockIdx.z * zc;
   const int32_t zEnd = min(lz0 + zc, p.extZ);
 
-  // cell (extended index 0, row 0, plane 0) of both buffers
+  // cell (extended index 0, row 0, plane 0) of both buffers, and from there
+  // the wave's rows: its own, and the halo row it stages into tT (ry == 0:
+  // below, ry == NY-1: above; the other waves re-read their own)
   const int64_t a0 = p.loX - p.allocX;
   const int64_t org = (p.loZ - p.allocZ) * p.plane + (p.loY - p.allocY) * p.pitch + a0 * 4;
-  const char *rowO = p.src + org + (int64_t)yo * p.pitch; // own row, plane 0
-  const char *rowM = p.src + org + (int64_t)ym * p.pitch;
-  const char *rowP = p.src + org + (int64_t)yp * p.pitch;
-  const char *cell = rowO + (int64_t)u * 16;
-  // the halo row this lane stages into tT (ry == 0: below, ry == NY-1: above)
-  const char *hcell = (ry == 0 ? rowM : rowP) + (int64_t)u * 16;
   const bool stagesHalo = ry == 0 || ry == NY - 1;
   const int32_t hrow = ry == 0 ? 0 : NY + 1;
-  char *dcell = p.dst + org + (int64_t)yo * p.pitch + (int64_t)u * 16;
+  const char *src0 = p.src + org;
+  const char *srcO = src0 + (int64_t)yo * p.pitch;
+  const char *srcH = src0 + (int64_t)(ry == 0 ? ym : ry == NY - 1 ? yp : yo) * p.pitch;
+  char *dstO = p.dst + org + (int64_t)yo * p.pitch;
+  const uint32_t voff = (uint32_t)u * 16u; // the lane's vector within a row
   const int32_t gx = (int32_t)p.loX + u * 4;
   const int32_t gy = (int32_t)p.loY + yo;
 
@@ -524,8 +595,6 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
   const int32_t last = under + p.trueExtX - 1;        // in vector body4-1
   const int32_t lastC = last & 3;                     // 3 - over
   const bool first = u == 0, lastLane = u == body4 - 1;
-  const int32_t leftOff = first ? last * 4 : -4;
-  const int32_t rightOff = lastLane ? (under - 4 * u) * 4 : 16;
   const bool wl1 = first && under == 1, wl2 = first && under == 2, wl3 = first && under == 3;
   const bool wr0 = lastLane && lastC == 0, wr1 = lastLane && lastC == 1,
              wr2 = lastLane && lastC == 2;
@@ -546,18 +615,29 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
   // just outside the tile, wrapped at the row's ends. Lane 0 computes the
   // t+1 value of eL, lane 1 that of eR.
   const int32_t rl = min(63, body4 - 1 - ub);
-  const int32_t eL = ub == 0 ? last : ub * 4 - 1;
-  const int32_t eR = ub + 63 >= body4 - 1 ? under : (ub + 64) * 4;
-  const int32_t eE = tx == 0 ? eL : eR;
-  const int32_t eXm = (eE == under ? last : eE - 1) * 4;
-  const int32_t eXp = (eE == last ? under : eE + 1) * 4;
-  const int32_t gxE = (int32_t)p.loX + eE;
+  const int32_t eL = f2_edge_left(ub, last), eR = f2_edge_right(ub, body4, under);
+  const int32_t gxE = (int32_t)p.loX + (tx == 0 ? eL : eR);
+  const bool rightEdge = tx >= rl;
+  // the lane's scalar of the gathered load, from cell 0 of row 0 of a plane
+  const uint32_t goff = f2_gather_offset(tx, eL, eR, under, last, yo, ym, yp, (uint32_t)p.pitch);
 
   // wrapped plane indices of the rolling window: i0 is the plane stage 1
   // produces this iteration, iP3 the plane requested in it
-  int32_t iM1 = pmod(lz0 - 2, p.extZ), i0 = pmod(lz0 - 1, p.extZ);
-  int32_t iP1 = pmod(lz0, p.extZ), iP2 = pmod(lz0 + 1, p.extZ), iP3 = pmod(lz0 + 2, p.extZ);
+  int32_t iM1 = f2_pmod(lz0 - 2, p.extZ), i0 = f2_pmod(lz0 - 1, p.extZ);
+  int32_t iP1 = f2_pmod(lz0, p.extZ), iP2 = f2_pmod(lz0 + 1, p.extZ),
+          iP3 = f2_pmod(lz0 + 2, p.extZ);
+  // The plane index is uniform, so row + plane is a scalar base
+  // (global_base) and the lane adds 32 bits.
   auto zoff = [&](int32_t i) { return (int64_t)i * p.plane; };
+  auto ld4 = [&](const char *row, int32_t i) {
+    const vfloat4 v = *(const __attribute__((address_space(1))) vfloat4 *)(
+        global_base(row + zoff(i)) + lane_offset(voff));
+    return make_float4(v.x, v.y, v.z, v.w);
+  };
+  auto gather = [&](int32_t i) {
+    return *(const __attribute__((address_space(1))) float *)(global_base(src0 + zoff(i)) +
+                                                              lane_offset(goff));
+  };
 
   // Vector loads run TWO planes ahead of their use (one plane per wave in
   // flight cannot cover HBM latency at 4 waves/SIMD): plane zz+1 and zz+2
@@ -568,16 +648,18 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
   // load queue there once per two planes. A variant without that drain,
   // every wait in the loop partial, measured the same step time, 0.532 vs
   // 0.532 ms in alternating runs: not kept.)
-  float4 cm = *(const float4 *)(cell + zoff(iM1));
-  float4 cc = *(const float4 *)(cell + zoff(i0));
-  float l = *(const float *)(cell + zoff(i0) + leftOff);
-  float r = *(const float *)(cell + zoff(i0) + rightOff);
+  float4 cm = ld4(srcO, iM1);
+  float4 cc = ld4(srcO, i0);
+  // gathered registers: g1 holds plane i0, g2 plane i0-1, g3 plane i0-2.
+  // Stage 1 needs g1 from the first iteration on; the first stage 2 (third
+  // iteration) needs g3 of plane lz0-1, which is this load, g2 of plane lz0
+  // and g1 of plane lz0+1, gathered in the first two iterations.
+  float g1 = gather(i0), g2 = g1, g3 = g1;
   tT[0][ry + 1][tx] = cc;
-  if (stagesHalo) tT[0][hrow][tx] = *(const float4 *)(hcell + zoff(i0));
-  float4 vA = *(const float4 *)(cell + zoff(iP1)), hA = *(const float4 *)(hcell + zoff(iP1));
-  float4 vB = *(const float4 *)(cell + zoff(iP2)), hB = *(const float4 *)(hcell + zoff(iP2));
+  if (stagesHalo) tT[0][hrow][tx] = ld4(srcH, i0);
+  float4 vA = ld4(srcO, iP1), hA = ld4(srcH, iP1);
+  float4 vB = ld4(srcO, iP2), hB = ld4(srcH, iP2);
   float4 sm = make_float4(0.f, 0.f, 0.f, 0.f), sc = sm;
-  float qxp = 0.f, qxm = 0.f, qyp = 0.f, qym = 0.f, qzp = 0.f, qzm = 0.f;
   __syncthreads();
   int tb = 0, sb = 0;
   // one plane: v / h hold plane zz+1 on entry and are re-requested with
@@ -586,33 +668,36 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
     const float4 cp = v, hp = h;
     // Requests, every lane and wave alike (a wait counts loads in issue
     // order, and only straight-line code lets the compiler count exactly).
-    // First what the NEXT iteration needs, all of it in planes already
-    // requested: the x scalars of plane zz+1 and, for lanes 0 / 1, the six
-    // t neighbours of their edge cell in plane zz (the other lanes load the
-    // same addresses as lane 1 and drop them).
-    const float ln = *(const float *)(cell + zoff(iP1) + leftOff);
-    const float rn = *(const float *)(cell + zoff(iP1) + rightOff);
-    const float nxp = *(const float *)(rowO + zoff(i0) + eXp);
-    const float nxm = *(const float *)(rowO + zoff(i0) + eXm);
-    const float nyp = *(const float *)(rowP + zoff(i0) + eE * 4);
-    const float nym = *(const float *)(rowM + zoff(i0) + eE * 4);
-    const float nzp = *(const float *)(rowO + zoff(iP1) + eE * 4);
-    const float nzm = *(const float *)(rowO + zoff(iM1) + eE * 4);
+    // First what the NEXT iteration needs, in a plane already requested:
+    // the gathered scalars of plane zz+1.
+    const float gn = gather(iP1);
     // then plane zz+3, last: a wait for the scalars above leaves it in flight
     // (waves that stage no halo row re-read their own vector)
-    v = *(const float4 *)(cell + zoff(iP3));
-    h = *(const float4 *)(hcell + zoff(iP3));
+    v = ld4(srcO, iP3);
+    h = ld4(srcH, iP3);
 
-    // stage 1: time t+1 of plane zz
+    // stage 1: time t+1 of plane zz. x neighbours across vectors: the
+    // neighbouring lanes' cc, at the tile's edges the t values of eL / eR
+    const float tL = lane_value(g1, F2_GATHER_SELF), tR = lane_value(g1, F2_GATHER_SELF + 1);
+    // (shifts first, selects after: a shift inside a branch of the select
+    // would run with the edge lanes switched off and miss their values)
+    const float l = lane_below(cc.w, tL);
+    const float ra = lane_above(cc.x);
+    const float r = rightEdge ? tR : ra;
     float4 s = stencil4(cc, l, r, tT[tb][ry + 2][tx], tT[tb][ry][tx], cp, cm);
     sphere4((int32_t)p.loZ + i0, s);
 
     // stage 2: time t+2 of plane zz-1, from the t+1 planes zz-2 (sm),
     // zz-1 (sc, tS[sb^1]) and zz (s)
     if (zz > lz0) {
+      // lanes 0 / 1: the six t neighbours of eL / eR in plane zz-1, summed
+      // +x -x +y -y +z -z (all lanes run the shifts, two keep the result)
+      const float e6 = ((((g2 + row_above<2>(g2)) + row_above<4>(g2)) + row_above<6>(g2)) +
+                        row_above<F2_GATHER_SELF>(g1)) +
+                       row_above<F2_GATHER_SELF>(g3);
       float e1 = 0.f;
       if (tx < 2) {
-        e1 = div6(qxp + qxm + qyp + qym + qzp + qzm);
+        e1 = div6(e6);
         const int32_t dy = gy - cY, dz = (int32_t)p.loZ + iM1 - cZ;
         const int32_t yz2 = dy * dy + dz * dz;
         const int32_t dxh = gxE - hotX, dxc = gxE - coldX;
@@ -621,16 +706,18 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
         else if ((int32_t)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad)
           e1 = 0.0f;
       }
-      const float eRight = __shfl(e1, 1);
-      const float l2 = tx == 0 ? e1 : tS[sb ^ 1][ry][max(tx - 1, 0)].w;
-      const float r2 = tx >= rl ? eRight : tS[sb ^ 1][ry][min(tx + 1, 63)].x;
+      const float eRight = lane_value(e1, 1);
+      const float l2 = lane_below(sc.w, e1);
+      const float ra2 = lane_above(sc.x);
+      const float r2 = rightEdge ? eRight : ra2;
       float4 out = stencil4(sc, l2, r2, tS[sb ^ 1][min(ry + 1, NY - 1)][tx],
                             tS[sb ^ 1][max(ry - 1, 0)][tx], s, sm);
       sphere4((int32_t)p.loZ + iM1, out);
       if (valid) {
-        typedef float vfloat4 __attribute__((ext_vector_type(4)));
         vfloat4 ov = {out.x, out.y, out.z, out.w};
-        __builtin_nontemporal_store(ov, (vfloat4 *)(dcell + zoff(iM1)));
+        __builtin_nontemporal_store(
+            ov, (__attribute__((address_space(1))) vfloat4 *)(global_base(dstO + zoff(iM1)) +
+                                                             lane_offset(voff)));
       }
     }
 
@@ -642,16 +729,11 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
     sb ^= 1;
     cm = cc;
     cc = cp;
-    l = ln;
-    r = rn;
     sm = sc;
     sc = s;
-    qxp = nxp;
-    qxm = nxm;
-    qyp = nyp;
-    qym = nym;
-    qzp = nzp;
-    qzm = nzm;
+    g3 = g2;
+    g2 = g1;
+    g1 = gn;
     iM1 = i0;
     i0 = iP1;
     iP1 = iP2;
@@ -918,9 +1000,10 @@ bool jacobi_wrap_eligible(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 
 }
 
 // Rows per block of jacobi_kernel_fuse2 (6 of them useful). 8 rows are 8
-// waves and 36 KB of LDS, so two blocks share a CU and one computes while
-// the other waits at its barrier; 14 rows (12 useful, 14% instead of 25%
-// redundant stage-1 rows, but one block per CU) measured 12% slower.
+// waves and 36 KB of LDS, so three blocks share a CU (two while the kernel
+// held 122 VGPRs) and the others compute while one waits at its barrier; 14
+// rows (12 useful, 14% instead of 25% redundant stage-1 rows, but one block
+// per CU) measured 12% slower at 122 VGPRs.
 constexpr int JAC_F2_NY = 8;
 
 // planes per block of the fused kernel; STENCIL_JAC_F2ZC overrides (read once)
@@ -952,6 +1035,8 @@ bool jacobi_fuse2_eligible(bool wrap, const LocalDomain &d, int64_t qi, const Re
   if (!row_extension(d, qi, region, /*mode=*/1, under, over)) return false;
   const Vec3 ext = region.extent();
   const dim3 g = jac_f2_grid(ext.x + under + over, ext.y, ext.z);
+  // the kernel's lane offsets are 32-bit and stay below one plane stride
+  if (d.curr(qi).plane() > 0x7fffffff) return false;
   return g.y <= 65535 && g.z <= 65535;
 }
 

@@ -5,7 +5,7 @@
 //   xz       : x + rolled z neighbors only (no y-row loads)
 //   full     : the real 7-point stencil
 //   full8    : 8 cells per thread (2 float4 strips)
-//   fuse2-NY : two time steps per pass, 64 x NY tile (see probe_fuse2)
+//   fuse2-8  : two time steps per pass, 64 x 8 tile (see probe_fuse2)
 // Usage: jacobi_probe [n=752] [rounds=10]
 #include <algorithm>
 #include <cstdio>
@@ -277,20 +277,54 @@ __global__ void __launch_bounds__(256) probe_prod(P p, const char *const *srcSlo
   }
 }
 
-// Two time steps per pass, the tile structure of the production
+// lane shifts and scalar bases as in csrc/src/jacobi.hip
+__device__ __forceinline__ float lane_below(float v, float first) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v),
+                                                    0x138 /* wave_shr:1 */, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float lane_above(float v) {
+  const int i = __float_as_int(v);
+  return __int_as_float(__builtin_amdgcn_update_dpp(i, i, 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+}
+template <int N> __device__ __forceinline__ float row_above(float v) {
+  return __int_as_float(
+      __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + N /* row_shl:N */, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float lane_value(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+typedef __attribute__((address_space(1))) char gchar;
+__device__ __forceinline__ gchar *global_base(const void *p) {
+  const uint64_t v = (uint64_t)p;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return (gchar *)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ uint32_t lane_offset(uint32_t o) {
+  asm volatile("" : "+v"(o));
+  return o;
+}
+
+// Two time steps per pass, the tile structure and the code of the production
 // jacobi_kernel_fuse2 (csrc/src/jacobi.hip) without its periodic wrap and
 // sphere sources: a 64 x NY block marching a chunk of zc planes computes
 // stage 1 (t+1) for all NY rows and stage 2 (t+2) for the inner NY-2; the t
 // rows and the t+1 rows sit in ping-pong LDS, the z planes of both stages
-// roll in registers, vector loads run two planes ahead. Lanes 0 / 1 of a row
-// compute the one t+1 cell just outside each x edge of the tile. Reads reach
-// 2 cells past the region on every side (the probe's 3-cell margin).
-// Usage of the variants: fuse2-8 / fuse2-14 = NY, zc = 64 planes.
+// roll in registers, vector loads run two planes ahead. x neighbours across
+// vectors come from the neighbouring lanes' registers; one gathered load per
+// wave and plane brings the t values of the cell just outside each x edge of
+// the tile and of its x / y neighbours (lane 2 j + side: +x -x +y -y self),
+// from which lanes 0 / 1 compute that cell's t+1 value. Every address is a
+// scalar base plus a 32-bit lane offset. Reads reach 2 cells past the region
+// on every side (the probe's 3-cell margin).
+// Usage of the variant: fuse2-8, zc = 64 planes. (NY = 14, one block per CU,
+// measured 1.115 against 1.083 ms before the lane shifts and was not ported.)
 template <int NY>
 __global__ void __launch_bounds__(64 * NY) probe_fuse2(P p, int32_t zc) {
   __shared__ float4 tT[2][NY + 2][64];
   __shared__ float4 tS[2][NY][64];
-  const int32_t tx = threadIdx.x, ry = threadIdx.y;
+  const int32_t tx = threadIdx.x;
+  const int32_t ry = __builtin_amdgcn_readfirstlane((int32_t)threadIdx.y);
   const int32_t ub = blockIdx.x * 64;
   const int32_t u0 = ub + tx;
   const int32_t u = min(u0, p.nx4 - 1);
@@ -299,18 +333,32 @@ __global__ void __launch_bounds__(64 * NY) probe_fuse2(P p, int32_t zc) {
   const bool valid = u0 < p.nx4 && ry >= 1 && ry <= NY - 2 && yb < p.ny;
   const int32_t z0 = blockIdx.z * zc;
   const int32_t zEnd = min(z0 + zc, p.nz);
-  const int64_t rowOff = (int64_t)(y + 3) * p.pitch + 16;
-  const char *cell = p.src + 3 * p.plane + rowOff + u * 16; // plane 0 of the region
-  const char *hcell = cell + (ry == 0 ? -p.pitch : ry == NY - 1 ? p.pitch : 0);
+  // row y - 1 of plane 0 of the region: every lane offset below is positive
+  const char *src0 = p.src + 3 * p.plane + (int64_t)(y + 2) * p.pitch;
+  char *dst0 = p.dst + 3 * p.plane + (int64_t)(y + 2) * p.pitch;
+  const uint32_t pitch = (uint32_t)p.pitch;
+  const uint32_t voff = pitch + 16u + (uint32_t)u * 16u;
+  const uint32_t hoff = voff + (ry == 0 ? -pitch : ry == NY - 1 ? pitch : 0u);
   const bool stagesHalo = ry == 0 || ry == NY - 1;
   const int32_t hrow = ry == 0 ? 0 : NY + 1;
-  char *dcell = p.dst + 3 * p.plane + rowOff + u * 16;
   const int32_t rl = min(63, p.nx4 - 1 - ub);
-  // cell index (floats from the row's first vector) of the edge cell
-  const int32_t eE = tx == 0 ? ub * 4 - 1 : (ub + rl + 1) * 4;
-  const char *erow = p.src + 3 * p.plane + rowOff + eE * 4;
+  const bool rightEdge = tx >= rl;
+  // cell index (floats from the row's first vector) of the two edge cells
+  const int32_t k = min(tx, 9), j = k >> 1;
+  const int32_t eE = (k & 1) ? (ub + rl + 1) * 4 : ub * 4 - 1;
+  const uint32_t goff = pitch + 16u + (uint32_t)(eE * 4) +
+                        (j == 0 ? 4u : j == 1 ? -4u : j == 2 ? pitch : j == 3 ? -pitch : 0u);
   const int32_t zLast = p.nz + 2; // last plane inside the allocation
   auto zoff = [&](int32_t z) { return (int64_t)min(z, zLast) * p.plane; };
+  auto ld4 = [&](uint32_t off, int32_t z) {
+    const vfloat4 v = *(const __attribute__((address_space(1))) vfloat4 *)(
+        global_base(src0 + zoff(z)) + lane_offset(off));
+    return make_float4(v.x, v.y, v.z, v.w);
+  };
+  auto gather = [&](int32_t z) {
+    return *(const __attribute__((address_space(1))) float *)(global_base(src0 + zoff(z)) +
+                                                              lane_offset(goff));
+  };
   auto stencil4 = [&](const float4 &c, float l, float r, const float4 &py, const float4 &my,
                       const float4 &pz, const float4 &mz) {
     float4 s;
@@ -321,42 +369,41 @@ __global__ void __launch_bounds__(64 * NY) probe_fuse2(P p, int32_t zc) {
     return s;
   };
   int32_t zi = z0 - 1; // plane of stage 1
-  float4 cm = *(const float4 *)(cell + zoff(zi - 1));
-  float4 cc = *(const float4 *)(cell + zoff(zi));
-  float l = *(const float *)(cell + zoff(zi) - 4);
-  float r = *(const float *)(cell + zoff(zi) + 16);
+  float4 cm = ld4(voff, zi - 1);
+  float4 cc = ld4(voff, zi);
+  float g1 = gather(zi), g2 = g1, g3 = g1;
   tT[0][ry + 1][tx] = cc;
-  if (stagesHalo) tT[0][hrow][tx] = *(const float4 *)(hcell + zoff(zi));
-  float4 vA = *(const float4 *)(cell + zoff(zi + 1)), hA = *(const float4 *)(hcell + zoff(zi + 1));
-  float4 vB = *(const float4 *)(cell + zoff(zi + 2)), hB = *(const float4 *)(hcell + zoff(zi + 2));
+  if (stagesHalo) tT[0][hrow][tx] = ld4(hoff, zi);
+  float4 vA = ld4(voff, zi + 1), hA = ld4(hoff, zi + 1);
+  float4 vB = ld4(voff, zi + 2), hB = ld4(hoff, zi + 2);
   float4 sm = {0.f, 0.f, 0.f, 0.f}, sc = sm;
-  float q0 = 0.f, q1 = 0.f, q2 = 0.f, q3 = 0.f, q4 = 0.f, q5 = 0.f;
   __syncthreads();
   int tb = 0, sb = 0;
   auto iteration = [&](int32_t zz, float4 &v, float4 &h) {
     const float4 cp = v, hp = h;
-    const float ln = *(const float *)(cell + zoff(zz + 1) - 4);
-    const float rn = *(const float *)(cell + zoff(zz + 1) + 16);
-    const float n0 = *(const float *)(erow + zoff(zz) + 4);
-    const float n1 = *(const float *)(erow + zoff(zz) - 4);
-    const float n2 = *(const float *)(erow + zoff(zz) + p.pitch);
-    const float n3 = *(const float *)(erow + zoff(zz) - p.pitch);
-    const float n4 = *(const float *)(erow + zoff(zz + 1));
-    const float n5 = *(const float *)(erow + zoff(zz - 1));
-    v = *(const float4 *)(cell + zoff(zz + 3));
-    h = *(const float4 *)(hcell + zoff(zz + 3));
+    const float gn = gather(zz + 1);
+    v = ld4(voff, zz + 3);
+    h = ld4(hoff, zz + 3);
+    const float l = lane_below(cc.w, lane_value(g1, 8));
+    const float ra = lane_above(cc.x);
+    const float r = rightEdge ? lane_value(g1, 9) : ra;
     const float4 s = stencil4(cc, l, r, tT[tb][ry + 2][tx], tT[tb][ry][tx], cp, cm);
     if (zz > z0) {
+      const float e6 = ((((g2 + row_above<2>(g2)) + row_above<4>(g2)) + row_above<6>(g2)) +
+                        row_above<8>(g1)) +
+                       row_above<8>(g3);
       float e1 = 0.f;
-      if (tx < 2) e1 = (q0 + q1 + q2 + q3 + q4 + q5) / 6.0f;
-      const float eRight = __shfl(e1, 1);
-      const float l2 = tx == 0 ? e1 : tS[sb ^ 1][ry][max(tx - 1, 0)].w;
-      const float r2 = tx >= rl ? eRight : tS[sb ^ 1][ry][min(tx + 1, 63)].x;
+      if (tx < 2) e1 = e6 / 6.0f;
+      const float l2 = lane_below(sc.w, e1);
+      const float ra2 = lane_above(sc.x);
+      const float r2 = rightEdge ? lane_value(e1, 1) : ra2;
       const float4 out = stencil4(sc, l2, r2, tS[sb ^ 1][min(ry + 1, NY - 1)][tx],
                                   tS[sb ^ 1][max(ry - 1, 0)][tx], s, sm);
       if (valid) {
         vfloat4 ov = {out.x, out.y, out.z, out.w};
-        __builtin_nontemporal_store(ov, (vfloat4 *)(dcell + zoff(zz - 1)));
+        __builtin_nontemporal_store(
+            ov, (__attribute__((address_space(1))) vfloat4 *)(global_base(dst0 + zoff(zz - 1)) +
+                                                             lane_offset(voff)));
       }
     }
     tS[sb][ry][tx] = s;
@@ -367,11 +414,11 @@ __global__ void __launch_bounds__(64 * NY) probe_fuse2(P p, int32_t zc) {
     sb ^= 1;
     cm = cc;
     cc = cp;
-    l = ln;
-    r = rn;
     sm = sc;
     sc = s;
-    q0 = n0, q1 = n1, q2 = n2, q3 = n3, q4 = n4, q5 = n5;
+    g3 = g2;
+    g2 = g1;
+    g1 = gn;
   };
   for (int32_t zz = z0 - 1; zz <= zEnd; zz += 2) {
     iteration(zz, vA, hA);
@@ -414,11 +461,10 @@ int main(int argc, char **argv) {
   dim3 grdsw(grd.x, grd.z, grd.y);
   const int f2zc = 64;
   dim3 grdf8((p.nx4 + 63) / 64, (p.ny + 5) / 6, (p.nz + f2zc - 1) / f2zc);
-  dim3 grdf14((p.nx4 + 63) / 64, (p.ny + 11) / 12, (p.nz + f2zc - 1) / f2zc);
-  const int NV = 13;
+  const int NV = 12;
   const char *names[NV] = {"copy", "xz",   "full",    "full8",   "prod-notail",
                            "prod+sph+tail", "prod+tail", "linstream", "full-plainst", "full-dispswap",
-                           "full-ldsrows", "fuse2-8", "fuse2-14"};
+                           "full-ldsrows", "fuse2-8"};
   double best[NV];
   for (int v = 0; v < NV; ++v) best[v] = 1e30;
   for (int r = 0; r < rounds; ++r) {
@@ -433,7 +479,6 @@ int main(int argc, char **argv) {
       case 9: hipLaunchKernelGGL(probe_swap, grdsw, blk, 0, 0, p); break;
       case 10: hipLaunchKernelGGL(probe_lds, grd, blk, 0, 0, p); break;
       case 11: hipLaunchKernelGGL(probe_fuse2<8>, grdf8, dim3(64, 8, 1), 0, 0, p, f2zc); break;
-      case 12: hipLaunchKernelGGL(probe_fuse2<14>, grdf14, dim3(64, 14, 1), 0, 0, p, f2zc); break;
       case 3: hipLaunchKernelGGL(probe8, grd8, blk, 0, 0, p); break;
       case 4:
         hipLaunchKernelGGL(probe_prod, grdp, blk, 0, 0, p, (const char *const *)slots,
