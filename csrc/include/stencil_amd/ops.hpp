@@ -28,6 +28,12 @@ namespace stencil_amd {
 // creators below check the same).
 void jacobi_step(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
                  const Rect3 &computeRegion, int streamId = 0, int extendVec = 0);
+// The kernel jacobi_step launches for these arguments, after the same checks
+// and launching nothing: "scalar", "vec4" (16 B strips with scalar head/tail
+// lanes), "vec4-all" (the same kernel, pure-vector over the extended row) or
+// "lds" (pure-vector, y rows staged in LDS); "none" for an empty region.
+const char *jacobi_step_kernel(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                               const Rect3 &computeRegion, int extendVec = 0);
 
 // fill an fp32 region with `value` (curr or next buffer); throws
 // std::invalid_argument, launching nothing, unless region is inside

@@ -328,6 +328,16 @@ PYBIND11_MODULE(_C, m) {
       },
       py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("region"),
       py::arg("compute_region"), py::arg("stream_id") = 0, py::arg("extend_vec") = 0);
+  m.def(
+      "jacobi_step_kernel",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                     const Rect3 &computeRegion, int extendVec) {
+        return value_errors([&] {
+          return std::string(jacobi_step_kernel(eng, dom, qi, region, computeRegion, extendVec));
+        });
+      },
+      py::arg("engine"), py::arg("dom"), py::arg("qi"), py::arg("region"),
+      py::arg("compute_region"), py::arg("extend_vec") = 0);
   m.def("fill_f32", [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
                                    float value, bool nextBuf) {
     value_errors([&] {

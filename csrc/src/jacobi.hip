@@ -41,6 +41,12 @@
 //     0.531 ms/step. STENCIL_JAC_FUSE2=0 forces single-step replays.
 // Hot/cold sphere sources match the reference's behavior (truncated-int
 // sqrtf distance, HOT=1/COLD=0 fixed cells) so results are comparable.
+// What the kernels share is written once: the sphere rule (SpheresT), the
+// scalar cell (scalar_cell), the six-neighbour sum in its fixed order with
+// the periodic x-end selects (stencil_sum4, XEnds), and in device_util.hpp
+// the nontemporal store, the lane shifts and the scalar-base addressing. On
+// the host one function decides every launch (plan_jacobi -> JacobiLaunch)
+// and one launches it (enqueue); the levers are in JacobiTuning.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -76,7 +82,7 @@ struct JacobiParams {
   // region to compute, global coords
   int64_t loX, loY, loZ;
   int32_t extX, extY, extZ;
-  int32_t vecAll; // 1 = pure-vector launch (see launch_jacobi_on)
+  int32_t vecAll; // 1 = pure-vector launch (see plan_jacobi)
   // whole compute region (for the hot/cold spheres)
   int64_t cLoX, cLoY, cLoZ, cHiX, cHiY, cHiZ;
 };
@@ -89,29 +95,123 @@ struct JacobiWrapParams : JacobiParams {
   int32_t trueExtX;
 };
 
-__device__ __forceinline__ bool sphere_override(int64_t x, int64_t y, int64_t z,
-                                                const JacobiParams &p, float &out) {
-  const int64_t cw = p.cHiX - p.cLoX;
-  const int64_t hotX = p.cLoX + cw / 3, coldX = p.cLoX + cw * 2 / 3;
-  const int64_t cY = (p.cLoY + p.cHiY) / 2, cZ = (p.cLoZ + p.cHiZ) / 2;
-  const int64_t r = cw / 10;
-  {
-    const int64_t dx = x - hotX, dy = y - cY, dz = z - cZ;
-    const int64_t d = (int64_t)__fsqrt_rn((float)(dx * dx + dy * dy + dz * dz));
-    if (d <= r) {
-      out = 1.0f;
-      return true;
-    }
+// The hot and cold sphere sources, one rule for every kernel: a cell whose
+// truncated-int sqrtf distance from (hotX, cY, cZ) is at most srad holds 1,
+// else one that close to (coldX, cY, cZ) holds 0. The truncation must match
+// the reference bit for bit. I = int32_t in the vector kernels (grids are far
+// below 2^31 per axis), int64_t in the scalar cells, which accept any shape.
+template <typename I> struct SpheresT {
+  I hotX, coldX, cY, cZ, srad;
+  __device__ __forceinline__ explicit SpheresT(const JacobiParams &p) {
+    const I cw = (I)(p.cHiX - p.cLoX);
+    hotX = (I)p.cLoX + cw / 3;
+    coldX = (I)p.cLoX + cw * 2 / 3;
+    cY = (I)(p.cLoY + p.cHiY) / 2;
+    cZ = (I)(p.cLoZ + p.cHiZ) / 2;
+    srad = cw / 10;
   }
-  {
-    const int64_t dx = x - coldX, dy = y - cY, dz = z - cZ;
-    const int64_t d = (int64_t)__fsqrt_rn((float)(dx * dx + dy * dy + dz * dz));
-    if (d <= r) {
-      out = 0.0f;
-      return true;
-    }
+  __device__ __forceinline__ I yz2(I gy, I gz) const {
+    const I dy = gy - cY, dz = gz - cZ;
+    return dy * dy + dz * dz;
   }
-  return false;
+  // the per-cell test: true, and `out` set, for a source cell
+  __device__ __forceinline__ bool cell(I gx, I yz2, float &out) const {
+    const I dxh = gx - hotX, dxc = gx - coldX;
+    const bool hot = (I)__fsqrt_rn((float)(dxh * dxh + yz2)) <= srad;
+    const bool cold = (I)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad;
+    out = hot ? 1.0f : cold ? 0.0f : out;
+    return hot || cold;
+  }
+  __device__ __forceinline__ bool cell(I gx, I gy, I gz, float &out) const {
+    return cell(gx, yz2(gy, gz), out);
+  }
+  // the 4 cells from gx on. The common case costs two int compares: with the
+  // truncated-int sqrt only yz2 >= (r+1)^2 guarantees exclusion
+  __device__ __forceinline__ void cells4(I gx, I gy, I gz, float4 &out) const {
+    const I q = yz2(gy, gz);
+    if (q >= (srad + 1) * (srad + 1)) return;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cell(gx + i, q, (&out.x)[i]);
+  }
+};
+using Spheres = SpheresT<int32_t>;
+
+// One cell of the scalar paths (jacobi_kernel, head / tail lanes of
+// jacobi_kernel_v4): the sphere value or the stencil, then the store. rowC /
+// rowD are the cell's row in src / dst, ax its index in the row.
+__device__ __forceinline__ void scalar_cell(const JacobiParams &p, const SpheresT<int64_t> &sph,
+                                            const char *rowC, char *rowD, int64_t ax, int64_t gx,
+                                            int64_t gy, int64_t gz) {
+  float out = 0.0f;
+  if (!sph.cell(gx, gy, gz, out)) {
+    const float px = *(const float *)(rowC + (ax + 1) * 4);
+    const float mx = *(const float *)(rowC + (ax - 1) * 4);
+    const float py = *(const float *)(rowC + p.pitch + ax * 4);
+    const float my = *(const float *)(rowC - p.pitch + ax * 4);
+    const float pz = *(const float *)(rowC + p.plane + ax * 4);
+    const float mz = *(const float *)(rowC - p.plane + ax * 4);
+    out = (px + mx + py + my + pz + mz) / 6.0f;
+  }
+  *(float *)(rowD + ax * 4) = out;
+}
+
+// The x ends of a row of float4 vectors: leftOff / rightOff are where a lane
+// finds the scalars across the ends of its vector, in bytes from the vector;
+// wl_k / wr_k tell that this scalar, not the component next to it, is the
+// -x / +x neighbour of component k.
+// WRAP = false: the scalars are the cells next to the vector in memory and
+// nothing is selected: compile-time constants, no select instruction.
+// WRAP = true (periodic rows under the vecAll row extension): the true first
+// cell is component `under` of the row's first vector (lane u == 0), the true
+// last cell, extended index `last`, component last & 3 of its last vector
+// (lane u == body4 - 1). Those two lanes load the periodic image of the row's
+// other end, and the one component whose in-vector neighbour is an overshoot
+// cell takes it.
+template <bool WRAP> struct XEnds;
+template <> struct XEnds<false> {
+  static constexpr int32_t leftOff = -4, rightOff = 16;
+  static constexpr bool wl1 = false, wl2 = false, wl3 = false;
+  static constexpr bool wr0 = false, wr1 = false, wr2 = false;
+  __device__ __forceinline__ XEnds() {}
+  __device__ __forceinline__ XEnds(const JacobiParams &, int32_t, int32_t) {}
+};
+template <> struct XEnds<true> {
+  int32_t under, last;
+  int32_t leftOff = -4, rightOff = 16;
+  bool wl1, wl2, wl3, wr0, wr1, wr2;
+  __device__ __forceinline__ XEnds(const JacobiWrapParams &p, int32_t u, int32_t body4) {
+    under = (int32_t)(p.trueLoX - p.loX); // 0..3
+    last = under + p.trueExtX - 1;        // in vector body4-1
+    const int32_t lastC = last & 3;       // 3 - over
+    const bool first = u == 0, lastLane = u == body4 - 1;
+    if (first) leftOff = last * 4;                // row start + last
+    if (lastLane) rightOff = (under - 4 * u) * 4; // row start + under
+    wl1 = first && under == 1;
+    wl2 = first && under == 2;
+    wl3 = first && under == 3;
+    wr0 = lastLane && lastC == 0;
+    wr1 = lastLane && lastC == 1;
+    wr2 = lastLane && lastC == 2;
+  }
+};
+
+// The six-neighbour sums of one vector, in the order every kernel and the
+// NumPy oracle sum in: +x -x +y -y +z -z. c is the vector's own plane (x
+// neighbours inside), l / r the scalars across its ends. Callers divide.
+template <bool WRAP>
+__device__ __forceinline__ float4 stencil_sum4(const XEnds<WRAP> &e, const float4 &c, float l,
+                                               float r, const float4 &py, const float4 &my,
+                                               const float4 &pz, const float4 &mz) {
+  float4 s;
+  s.x = (e.wr0 ? r : c.y) + l + py.x + my.x + pz.x + mz.x;
+  s.y = (e.wr1 ? r : c.z) + (e.wl1 ? l : c.x) + py.y + my.y + pz.y + mz.y;
+  s.z = (e.wr2 ? r : c.w) + (e.wl2 ? l : c.y) + py.z + my.z + pz.z + mz.z;
+  s.w = r + (e.wl3 ? l : c.z) + py.w + my.w + pz.w + mz.w;
+  return s;
+}
+// the single-step kernels' division (fuse2 divides with div6)
+__device__ __forceinline__ float4 over6(const float4 &s) {
+  return make_float4(s.x / 6.0f, s.y / 6.0f, s.z / 6.0f, s.w / 6.0f);
 }
 
 // Vectorized z-marching kernel for wide regions: each thread owns a
@@ -137,43 +237,15 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4(JacobiParams p) {
   const int64_t ay = gy - p.allocY;
   const int32_t zEnd = min((int32_t)(lz0 + JAC_ZCHUNK), p.extZ);
 
-  // sphere geometry (int32: grids are far below 2^31 per axis)
-  const int32_t cw = (int32_t)(p.cHiX - p.cLoX);
-  const int32_t hotX = (int32_t)p.cLoX + cw / 3, coldX = (int32_t)p.cLoX + cw * 2 / 3;
-  const int32_t cY = (int32_t)(p.cLoY + p.cHiY) / 2, cZ = (int32_t)(p.cLoZ + p.cHiZ) / 2;
-  const int32_t srad = cw / 10;
+  const Spheres sph(p);
+  const SpheresT<int64_t> sph64(p);
+  const XEnds<false> ends;
 
-  auto sphere4 = [&](int32_t gx, int32_t gyy, int32_t gzz, float4 &out) {
-    const int32_t dy = gyy - cY, dz = gzz - cZ;
-    const int32_t yz2 = dy * dy + dz * dz;
-    // truncated-int sqrt: only yz2 >= (r+1)^2 guarantees exclusion
-    if (yz2 >= (srad + 1) * (srad + 1)) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int32_t dxh = gx + i - hotX, dxc = gx + i - coldX;
-      if ((int32_t)__fsqrt_rn((float)(dxh * dxh + yz2)) <= srad)
-        (&out.x)[i] = 1.0f;
-      else if ((int32_t)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad)
-        (&out.x)[i] = 0.0f;
-    }
-  };
-
-  auto scalar_cell = [&](int32_t lx, int32_t lz) {
+  auto cell = [&](int32_t lx, int32_t lz) {
     const int64_t gx = p.loX + lx;
     const int64_t gz = p.loZ + lz;
-    const int64_t ax = gx - p.allocX, az = gz - p.allocZ;
-    const char *rowC = srcBase + az * p.plane + ay * p.pitch;
-    float out;
-    if (!sphere_override(gx, gy, gz, p, out)) {
-      const float px = *(const float *)(rowC + (ax + 1) * 4);
-      const float mx = *(const float *)(rowC + (ax - 1) * 4);
-      const float py = *(const float *)(rowC + p.pitch + ax * 4);
-      const float my = *(const float *)(rowC - p.pitch + ax * 4);
-      const float pz = *(const float *)(rowC + p.plane + ax * 4);
-      const float mz = *(const float *)(rowC - p.plane + ax * 4);
-      out = (px + mx + py + my + pz + mz) / 6.0f;
-    }
-    *(float *)(dstBase + az * p.plane + ay * p.pitch + ax * 4) = out;
+    const int64_t row = (gz - p.allocZ) * p.plane + ay * p.pitch;
+    scalar_cell(p, sph64, srcBase + row, dstBase + row, gx - p.allocX, gx, gy, gz);
   };
 
   const int64_t a0 = p.loX - p.allocX;
@@ -207,16 +279,9 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4(JacobiParams p) {
       const float right = *(const float *)(col + 16);
       const float4 py = *(const float4 *)(col + p.pitch);
       const float4 my = *(const float4 *)(col - p.pitch);
-      float4 out;
-      out.x = (cc.y + left + py.x + my.x + cp.x + cm.x) / 6.0f;
-      out.y = (cc.z + cc.x + py.y + my.y + cp.y + cm.y) / 6.0f;
-      out.z = (cc.w + cc.y + py.z + my.z + cp.z + cm.z) / 6.0f;
-      out.w = (right + cc.z + py.w + my.w + cp.w + cm.w) / 6.0f;
-      sphere4(gx, (int32_t)gy, (int32_t)(p.loZ + lz), out);
-      // next is write-only this iteration: bypass cache pollution
-      typedef float vfloat4 __attribute__((ext_vector_type(4)));
-      vfloat4 ov = {out.x, out.y, out.z, out.w};
-      __builtin_nontemporal_store(ov, (vfloat4 *)dcol);
+      float4 out = over6(stencil_sum4(ends, cc, left, right, py, my, cp, cm));
+      sph.cells4(gx, (int32_t)gy, (int32_t)(p.loZ + lz), out);
+      store4(dcol, out); // next is write-only this iteration
       cm = cc;
       cc = cp;
       col += p.plane;
@@ -227,10 +292,10 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4(JacobiParams p) {
     // SLOWER overall -- the extra block column cost more than the
     // straggler lane; keep the compact form)
     for (int32_t lz = lz0; lz < zEnd; ++lz)
-      for (int32_t lx = 0; lx < head; ++lx) scalar_cell(lx, lz);
+      for (int32_t lx = 0; lx < head; ++lx) cell(lx, lz);
   } else if (u == body4 + 1) {
     for (int32_t lz = lz0; lz < zEnd; ++lz)
-      for (int32_t lx = p.extX - tail; lx < p.extX; ++lx) scalar_cell(lx, lz);
+      for (int32_t lx = p.extX - tail; lx < p.extX; ++lx) cell(lx, lz);
   }
 }
 
@@ -261,13 +326,13 @@ __global__ void __launch_bounds__(256) jacobi_kernel_v4(JacobiParams p) {
 // store garbage. The launcher only extends a row when every overshoot cell
 // is an x-halo cell or a pitch-slack byte of that row (row_extension), which
 // nothing on this path reads; a row without that room never gets here
-// (jacobi_wrap_eligible answers false).
+// (plan_jacobi plans no WrapStep for it).
 // gfx950 resource usage (-Rpass-analysis=kernel-resource-usage), the same
 // for ZC = 16 and 32:
 //   WRAP=false: 58 VGPRs, 54 SGPRs, 0 scratch, 8 waves/SIMD, 12288 B LDS
-//   WRAP=true : 58 VGPRs, 58 SGPRs, 0 scratch, 8 waves/SIMD, 12288 B LDS
+//   WRAP=true : 60 VGPRs, 58 SGPRs, 0 scratch, 8 waves/SIMD, 12288 B LDS
 // (the row/plane selects and the six x-select lane masks live in scalar
-// registers; the WRAP=false instruction stream is unchanged by the flag)
+// registers; WRAP=false has no select for the x ends, see XEnds)
 template <int ZC, bool WRAP = false>
 __global__ void __launch_bounds__(256)
 jacobi_kernel_v4_lds(std::conditional_t<WRAP, JacobiWrapParams, JacobiParams> p) {
@@ -290,20 +355,19 @@ jacobi_kernel_v4_lds(std::conditional_t<WRAP, JacobiWrapParams, JacobiParams> p)
   const int32_t zEnd = min((int32_t)(lz0 + ZC), p.extZ);
   // byte offsets from a lane's own cell to the rows/planes it stages:
   //   myHalo: -y row staged by ry==0      pyHalo: +y row staged by ry==3
-  //   mzOff : the initial -z plane        (+z plane: colP, in the loop)
-  int64_t myHalo = 0, pyHalo, mzOff = 0;
+  //   mzOff : the initial -z plane        (+z plane: pzOff, in the loop)
+  int64_t myHalo = -p.pitch, pyHalo, mzOff = -p.plane;
   if constexpr (WRAP) {
     // all three depend on blockIdx only: scalar registers
     const int32_t by0 = blockIdx.y * 4, by3 = by0 + 3;
     const int64_t ySpan = (int64_t)(p.extY - 1) * p.pitch;
-    myHalo = by0 == 0 ? ySpan : -p.pitch;
+    if (by0 == 0) myHalo = ySpan;
     // ry==3 at the last row wraps down to row 0; past it the lane already
     // sits on row 0 and any in-range row will do
     pyHalo = by3 < p.extY - 1 ? p.pitch : (by3 == p.extY - 1 ? -ySpan : 0);
-    mzOff = lz0 == 0 ? (int64_t)(p.extZ - 1) * p.plane : -p.plane;
+    if (lz0 == 0) mzOff = (int64_t)(p.extZ - 1) * p.plane;
   } else {
-    // +y halo row staged by ry==3: one past its own row, clamped in-bounds
-    // (the -y row and -z plane are the fixed - p.pitch / - p.plane)
+    // one past its own row, clamped in-bounds
     pyHalo = (ly < p.extY) ? p.pitch : 0;
   }
 
@@ -316,95 +380,31 @@ jacobi_kernel_v4_lds(std::conditional_t<WRAP, JacobiWrapParams, JacobiParams> p)
   const char *col = p.src + az0 * p.plane + ay * p.pitch + ax * 4;
   char *dcol = p.dst + az0 * p.plane + ay * p.pitch + ax * 4;
 
-  const int32_t cw = (int32_t)(p.cHiX - p.cLoX);
-  const int32_t hotX = (int32_t)p.cLoX + cw / 3, coldX = (int32_t)p.cLoX + cw * 2 / 3;
-  const int32_t cY = (int32_t)(p.cLoY + p.cHiY) / 2, cZ = (int32_t)(p.cLoZ + p.cHiZ) / 2;
-  const int32_t srad = cw / 10;
-  auto sphere4 = [&](int32_t gzz, float4 &out) {
-    const int32_t dy = (int32_t)gy - cY, dz = gzz - cZ;
-    const int32_t yz2 = dy * dy + dz * dz;
-    if (yz2 >= (srad + 1) * (srad + 1)) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int32_t dxh = gx + i - hotX, dxc = gx + i - coldX;
-      if ((int32_t)__fsqrt_rn((float)(dxh * dxh + yz2)) <= srad)
-        (&out.x)[i] = 1.0f;
-      else if ((int32_t)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad)
-        (&out.x)[i] = 0.0f;
-    }
-  };
+  const Spheres sph(p);
+  const XEnds<WRAP> ends(p, u, body4);
 
-  // WRAP x axis: where the first / last lane of a row find the periodic
-  // neighbour of the row's true end cells, and which component takes it
-  int32_t leftOff = -4, rightOff = 16;
-  bool wl1 = false, wl2 = false, wl3 = false; // left -> -x of component k
-  bool wr0 = false, wr1 = false, wr2 = false; // right -> +x of component k
-  if constexpr (WRAP) {
-    const int32_t under = (int32_t)(p.trueLoX - p.loX); // 0..3
-    const int32_t last = under + p.trueExtX - 1;        // in vector body4-1
-    const int32_t lastC = last & 3;                     // 3 - over
-    const bool first = u == 0, lastLane = u == body4 - 1;
-    if (first) leftOff = last * 4;                // row start + last
-    if (lastLane) rightOff = (under - 4 * u) * 4; // row start + under
-    wl1 = first && under == 1;
-    wl2 = first && under == 2;
-    wl3 = first && under == 3;
-    wr0 = lastLane && lastC == 0;
-    wr1 = lastLane && lastC == 1;
-    wr2 = lastLane && lastC == 2;
-  }
-
-  float4 cm, cc;
-  if constexpr (WRAP) {
-    cm = *(const float4 *)(col + mzOff);
-    cc = *(const float4 *)(col);
-    tile[0][ry + 1][tx] = cc;
-    if (ry == 0) tile[0][0][tx] = *(const float4 *)(col + myHalo);
-  } else {
-    cm = *(const float4 *)(col - p.plane);
-    cc = *(const float4 *)(col);
-    tile[0][ry + 1][tx] = cc;
-    if (ry == 0) tile[0][0][tx] = *(const float4 *)(col - p.pitch);
-  }
+  float4 cm = *(const float4 *)(col + mzOff);
+  float4 cc = *(const float4 *)(col);
+  tile[0][ry + 1][tx] = cc;
+  if (ry == 0) tile[0][0][tx] = *(const float4 *)(col + myHalo);
   if (ry == 3) tile[0][5][tx] = *(const float4 *)(col + pyHalo);
   __syncthreads();
   int buf = 0;
   for (int32_t lz = lz0; lz < zEnd; ++lz) {
-    // +z plane and the -y row in it; WRAP: uniform per iteration
-    const char *colP, *colPmy;
-    float left, right;
-    if constexpr (WRAP) {
-      colP = col + (lz == p.extZ - 1 ? -(int64_t)(p.extZ - 1) * p.plane : p.plane);
-      colPmy = colP + myHalo;
-      left = *(const float *)(col + leftOff);
-      right = *(const float *)(col + rightOff);
-    } else {
-      colP = col + p.plane;
-      colPmy = col + p.plane - p.pitch;
-      left = *(const float *)(col - 4);
-      right = *(const float *)(col + 16);
-    }
+    // +z plane (WRAP: plane 0 after the last one, uniform per iteration) and
+    // the -y row in it
+    const int64_t pzOff =
+        WRAP && lz == p.extZ - 1 ? -(int64_t)(p.extZ - 1) * p.plane : p.plane;
+    const char *colP = col + pzOff, *colPmy = colP + myHalo;
+    const float left = *(const float *)(col + ends.leftOff);
+    const float right = *(const float *)(col + ends.rightOff);
     const float4 cp = *(const float4 *)colP;
     const float4 py = tile[buf][ry + 2][tx];
     const float4 my = tile[buf][ry][tx];
-    float4 out;
-    if constexpr (WRAP) {
-      out.x = ((wr0 ? right : cc.y) + left + py.x + my.x + cp.x + cm.x) / 6.0f;
-      out.y = ((wr1 ? right : cc.z) + (wl1 ? left : cc.x) + py.y + my.y + cp.y + cm.y) / 6.0f;
-      out.z = ((wr2 ? right : cc.w) + (wl2 ? left : cc.y) + py.z + my.z + cp.z + cm.z) / 6.0f;
-      out.w = (right + (wl3 ? left : cc.z) + py.w + my.w + cp.w + cm.w) / 6.0f;
-    } else {
-      out.x = (cc.y + left + py.x + my.x + cp.x + cm.x) / 6.0f;
-      out.y = (cc.z + cc.x + py.y + my.y + cp.y + cm.y) / 6.0f;
-      out.z = (cc.w + cc.y + py.z + my.z + cp.z + cm.z) / 6.0f;
-      out.w = (right + cc.z + py.w + my.w + cp.w + cm.w) / 6.0f;
-    }
-    sphere4((int32_t)(p.loZ + lz), out);
-    if (valid) {
-      typedef float vfloat4 __attribute__((ext_vector_type(4)));
-      vfloat4 ov = {out.x, out.y, out.z, out.w};
-      __builtin_nontemporal_store(ov, (vfloat4 *)dcol);
-    }
+    float4 out = over6(stencil_sum4(ends, cc, left, right, py, my, cp, cm));
+    sph.cells4(gx, (int32_t)gy, (int32_t)(p.loZ + lz), out);
+    if (valid) store4(dcol, out);
+
     tile[buf ^ 1][ry + 1][tx] = cp;
     if (ry == 0) tile[buf ^ 1][0][tx] = *(const float4 *)colPmy;
     if (ry == 3) tile[buf ^ 1][5][tx] = *(const float4 *)(colP + pyHalo);
@@ -415,49 +415,6 @@ jacobi_kernel_v4_lds(std::conditional_t<WRAP, JacobiWrapParams, JacobiParams> p)
     col += p.plane;
     dcol += p.plane;
   }
-}
-
-// Lane shifts of one VGPR by data-parallel-primitive moves (no LDS, no
-// memory). Every lane of the wave must be active where they are used.
-//   lane_below: lane i gets v of lane i-1 of the wave, lane 0 gets `first`
-//   lane_above: lane i gets v of lane i+1 of the wave, lane 63 keeps its own
-//   row_above<N>: lane i gets lane i+N of its 16-lane row (0 past the row)
-__device__ __forceinline__ float lane_below(float v, float first) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v),
-                                                    0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float lane_above(float v) {
-  const int i = __float_as_int(v);
-  return __int_as_float(__builtin_amdgcn_update_dpp(i, i, 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
-}
-template <int N> __device__ __forceinline__ float row_above(float v) {
-  static_assert(N >= 1 && N <= 15, "row shift");
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + N /* row_shl:N */, 0xf, 0xf, true));
-}
-// A wave-uniform address as a scalar-register base in the GLOBAL address
-// space: the loads and the store below then take the form scalar base +
-// 32-bit lane offset. (Through a generic pointer they would become flat
-// instructions, and without the pin the compiler folds the lane offset into a
-// per-lane 64-bit pointer and multiplies per load.)
-typedef float vfloat4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) char gchar;
-__device__ __forceinline__ gchar *global_base(const void *p) {
-  const uint64_t v = (uint64_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return (gchar *)(((uint64_t)hi << 32) | lo);
-}
-// A loop-invariant 32-bit lane offset, made opaque at its use: the zero
-// extension then stays next to the access, where instruction selection folds
-// it into the scalar-base form; hoisted out of the loop it becomes a 64-bit
-// register pair and a 64-bit vector add per access.
-__device__ __forceinline__ uint32_t lane_offset(uint32_t o) {
-  asm volatile("" : "+v"(o));
-  return o;
-}
-__device__ __forceinline__ float lane_value(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
 // Two time steps in one pass over memory, for the same launch the WRAP
@@ -503,7 +460,7 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
 // Addresses: every load and the store is a wave-uniform 64-bit base (buffer
 // + row + plane, scalar unit) plus a 32-bit lane offset that never changes
 // (the global saddr + voffset form); the gathered offset is below the plane
-// stride, which jacobi_fuse2_eligible bounds to 31 bits.
+// stride, which plan_jacobi bounds to 31 bits.
 // Periodic wrap is a true modulo on every axis (rows and planes by index,
 // x by the row's true first/last cell), so extents down to x=8, y=1, z=1
 // are exact; the sphere override runs after each stage at the WRAPPED
@@ -520,8 +477,9 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
 // The division is div6 (device_util.hpp): 3 instructions per value instead
 // of the IEEE expansion's 11, the same bits.
 // gfx950 resource usage (-Rpass-analysis=kernel-resource-usage), NY = 8:
-//   78 VGPRs, 78 SGPRs, 0 scratch, 6 waves/SIMD, 36864 B LDS: three blocks
-//   (24 waves) per CU, bound by the VGPRs (80 is the most for 6 waves/SIMD).
+//   76 VGPRs, 84 SGPRs, 0 scratch, 6 waves/SIMD, 36864 B LDS: three blocks
+//   (24 waves) per CU, bound by the VGPRs (80 is the most for 6 waves/SIMD;
+//   78 / 78 while the sphere test was branches, now it is selects).
 //   Before the lane shifts and the gathered load: 122 VGPRs, 82 SGPRs, two
 //   blocks per CU.
 // The loop body, two planes, every block of it counted (the IEEE-division
@@ -533,6 +491,9 @@ __device__ __forceinline__ float lane_value(float v, int lane) {
 //   v_mov_b32_dpp 0 -> 18, v_readlane_b32 0 -> 6. Every global access has the
 //   saddr + voffset form. The load queue is still drained once per two
 //   planes at the loop latch, where the register slots are copied.
+//   (Since the sphere test is the shared select form instead of a branch per
+//   cell the body is 941 instead of 1012 instructions, fewer moves among
+//   them; every memory, LDS, DPP and readlane count above is unchanged.)
 // Measured at 750^3 (profiles/README.md, "Fused two-step jacobi graph").
 template <int NY>
 __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams p) {
@@ -571,55 +532,22 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
   const int32_t gx = (int32_t)p.loX + u * 4;
   const int32_t gy = (int32_t)p.loY + yo;
 
-  const int32_t cw = (int32_t)(p.cHiX - p.cLoX);
-  const int32_t hotX = (int32_t)p.cLoX + cw / 3, coldX = (int32_t)p.cLoX + cw * 2 / 3;
-  const int32_t cY = (int32_t)(p.cLoY + p.cHiY) / 2, cZ = (int32_t)(p.cLoZ + p.cHiZ) / 2;
-  const int32_t srad = cw / 10;
-  auto sphere4 = [&](int32_t gzz, float4 &out) {
-    const int32_t dy = gy - cY, dz = gzz - cZ;
-    const int32_t yz2 = dy * dy + dz * dz;
-    if (yz2 >= (srad + 1) * (srad + 1)) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int32_t dxh = gx + i - hotX, dxc = gx + i - coldX;
-      if ((int32_t)__fsqrt_rn((float)(dxh * dxh + yz2)) <= srad)
-        (&out.x)[i] = 1.0f;
-      else if ((int32_t)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad)
-        (&out.x)[i] = 0.0f;
-    }
-  };
-
-  // x wrap of the row's true end cells, as in the WRAP kernel: extended
-  // index `under` is the first true cell, `last` the last one
-  const int32_t under = (int32_t)(p.trueLoX - p.loX); // 0..3
-  const int32_t last = under + p.trueExtX - 1;        // in vector body4-1
-  const int32_t lastC = last & 3;                     // 3 - over
-  const bool first = u == 0, lastLane = u == body4 - 1;
-  const bool wl1 = first && under == 1, wl2 = first && under == 2, wl3 = first && under == 3;
-  const bool wr0 = lastLane && lastC == 0, wr1 = lastLane && lastC == 1,
-             wr2 = lastLane && lastC == 2;
-  // one stencil evaluation of a vector: c its own plane (x neighbours
-  // inside), l / r the scalars across its ends, then +y -y +z -z
-  auto stencil4 = [&](const float4 &c, float l, float r, const float4 &py, const float4 &my,
-                      const float4 &pz, const float4 &mz) {
-    float4 s;
-    s.x = ((wr0 ? r : c.y) + l + py.x + my.x + pz.x + mz.x);
-    s.y = ((wr1 ? r : c.z) + (wl1 ? l : c.x) + py.y + my.y + pz.y + mz.y);
-    s.z = ((wr2 ? r : c.w) + (wl2 ? l : c.y) + py.z + my.z + pz.z + mz.z);
-    s.w = (r + (wl3 ? l : c.z) + py.w + my.w + pz.w + mz.w);
-    return div6(s);
-  };
+  const Spheres sph(p);
+  // x wrap of the row's true end cells: extended index ends.under is the
+  // first true cell, ends.last the last one
+  const XEnds<true> ends(p, u, body4);
 
   // tile x edges (uniform per block): rl is the last lane that holds a
   // vector of its own; eL / eR are the extended indices of the true cells
   // just outside the tile, wrapped at the row's ends. Lane 0 computes the
   // t+1 value of eL, lane 1 that of eR.
   const int32_t rl = min(63, body4 - 1 - ub);
-  const int32_t eL = f2_edge_left(ub, last), eR = f2_edge_right(ub, body4, under);
+  const int32_t eL = f2_edge_left(ub, ends.last), eR = f2_edge_right(ub, body4, ends.under);
   const int32_t gxE = (int32_t)p.loX + (tx == 0 ? eL : eR);
   const bool rightEdge = tx >= rl;
   // the lane's scalar of the gathered load, from cell 0 of row 0 of a plane
-  const uint32_t goff = f2_gather_offset(tx, eL, eR, under, last, yo, ym, yp, (uint32_t)p.pitch);
+  const uint32_t goff =
+      f2_gather_offset(tx, eL, eR, ends.under, ends.last, yo, ym, yp, (uint32_t)p.pitch);
 
   // wrapped plane indices of the rolling window: i0 is the plane stage 1
   // produces this iteration, iP3 the plane requested in it
@@ -684,8 +612,8 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
     const float l = lane_below(cc.w, tL);
     const float ra = lane_above(cc.x);
     const float r = rightEdge ? tR : ra;
-    float4 s = stencil4(cc, l, r, tT[tb][ry + 2][tx], tT[tb][ry][tx], cp, cm);
-    sphere4((int32_t)p.loZ + i0, s);
+    float4 s = div6(stencil_sum4(ends, cc, l, r, tT[tb][ry + 2][tx], tT[tb][ry][tx], cp, cm));
+    sph.cells4(gx, gy, (int32_t)p.loZ + i0, s);
 
     // stage 2: time t+2 of plane zz-1, from the t+1 planes zz-2 (sm),
     // zz-1 (sc, tS[sb^1]) and zz (s)
@@ -698,27 +626,16 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
       float e1 = 0.f;
       if (tx < 2) {
         e1 = div6(e6);
-        const int32_t dy = gy - cY, dz = (int32_t)p.loZ + iM1 - cZ;
-        const int32_t yz2 = dy * dy + dz * dz;
-        const int32_t dxh = gxE - hotX, dxc = gxE - coldX;
-        if ((int32_t)__fsqrt_rn((float)(dxh * dxh + yz2)) <= srad)
-          e1 = 1.0f;
-        else if ((int32_t)__fsqrt_rn((float)(dxc * dxc + yz2)) <= srad)
-          e1 = 0.0f;
+        sph.cell(gxE, gy, (int32_t)p.loZ + iM1, e1);
       }
       const float eRight = lane_value(e1, 1);
       const float l2 = lane_below(sc.w, e1);
       const float ra2 = lane_above(sc.x);
       const float r2 = rightEdge ? eRight : ra2;
-      float4 out = stencil4(sc, l2, r2, tS[sb ^ 1][min(ry + 1, NY - 1)][tx],
-                            tS[sb ^ 1][max(ry - 1, 0)][tx], s, sm);
-      sphere4((int32_t)p.loZ + iM1, out);
-      if (valid) {
-        vfloat4 ov = {out.x, out.y, out.z, out.w};
-        __builtin_nontemporal_store(
-            ov, (__attribute__((address_space(1))) vfloat4 *)(global_base(dstO + zoff(iM1)) +
-                                                             lane_offset(voff)));
-      }
+      float4 out = div6(stencil_sum4(ends, sc, l2, r2, tS[sb ^ 1][min(ry + 1, NY - 1)][tx],
+                                     tS[sb ^ 1][max(ry - 1, 0)][tx], s, sm));
+      sph.cells4(gx, gy, (int32_t)p.loZ + iM1, out);
+      if (valid) store4(global_base(dstO + zoff(iM1)) + lane_offset(voff), out);
     }
 
     tS[sb][ry][tx] = s;
@@ -750,6 +667,7 @@ __global__ void __launch_bounds__(64 * NY) jacobi_kernel_fuse2(JacobiWrapParams 
 __global__ void jacobi_kernel(JacobiParams p) {
   const char *srcBase = p.src;
   char *dstBase = p.dst;
+  const SpheresT<int64_t> sph(p);
   const int64_t total = (int64_t)p.extX * p.extY * p.extZ;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
@@ -761,18 +679,8 @@ __global__ void jacobi_kernel(JacobiParams p) {
     const int64_t gx = p.loX + lx, gy = p.loY + ly, gz = p.loZ + lz;
     // allocation-local element coords
     const int64_t ax = gx - p.allocX, ay = gy - p.allocY, az = gz - p.allocZ;
-    const char *rowC = srcBase + az * p.plane + ay * p.pitch;
-    float out;
-    if (!sphere_override(gx, gy, gz, p, out)) {
-      const float px = *(const float *)(rowC + (ax + 1) * 4);
-      const float mx = *(const float *)(rowC + (ax - 1) * 4);
-      const float py = *(const float *)(rowC + p.pitch + ax * 4);
-      const float my = *(const float *)(rowC - p.pitch + ax * 4);
-      const float pz = *(const float *)(rowC + p.plane + ax * 4);
-      const float mz = *(const float *)(rowC - p.plane + ax * 4);
-      out = (px + mx + py + my + pz + mz) / 6.0f;
-    }
-    *(float *)(dstBase + az * p.plane + ay * p.pitch + ax * 4) = out;
+    const int64_t row = az * p.plane + ay * p.pitch;
+    scalar_cell(p, sph, srcBase + row, dstBase + row, ax, gx, gy, gz);
   }
 }
 
@@ -789,19 +697,40 @@ __global__ void fill_kernel(char *base, int64_t pitch, int64_t plane,
   }
 }
 
-} // namespace
+// The levers, all from the environment. The tuning values are read once per
+// process. The two path switches are the A/B levers and the fallbacks: they
+// are read at each graph creation, which is set-up and never on the step path.
+struct JacobiTuning {
+  bool lds = true;     // STENCIL_JAC_LDS=0 turns the LDS-rows kernel off
+  int zc = 32;         // STENCIL_JAC_ZC=16: its planes per block (32 measured +1.8%)
+  int bx = 64, by = 4; // STENCIL_JAC_BLOCK=<bx>x<by>, 256 threads: jacobi_kernel_v4's block
+  int f2zc = 64;       // STENCIL_JAC_F2ZC=<n >= 1>: planes per block of the fused kernel
 
-namespace {
-
-// STENCIL_JAC_LDS=0 turns the LDS-rows kernel off (read once)
-bool jac_use_lds() {
-  static int useLds = -1;
-  if (useLds < 0) {
-    const char *e = getenv("STENCIL_JAC_LDS");
-    useLds = (e && e[0] == '0') ? 0 : 1;
+  static const JacobiTuning &get() {
+    static const JacobiTuning tuning = [] {
+      JacobiTuning t;
+      t.lds = !is_zero("STENCIL_JAC_LDS");
+      if (const char *e = getenv("STENCIL_JAC_ZC")) t.zc = atoi(e) == 16 ? 16 : 32;
+      if (const char *e = getenv("STENCIL_JAC_BLOCK")) {
+        int bx, by;
+        if (sscanf(e, "%dx%d", &bx, &by) == 2 && bx * by == 256) t.bx = bx, t.by = by;
+      }
+      if (const char *e = getenv("STENCIL_JAC_F2ZC")) t.f2zc = atoi(e) >= 1 ? atoi(e) : 64;
+      return t;
+    }();
+    return tuning;
   }
-  return useLds != 0;
-}
+  // STENCIL_JAC_WRAP=0 forces the translate graph, STENCIL_JAC_FUSE2=0
+  // single-step replays
+  static bool wrap() { return !is_zero("STENCIL_JAC_WRAP"); }
+  static bool fuse2() { return !is_zero("STENCIL_JAC_FUSE2"); }
+
+private:
+  static bool is_zero(const char *name) {
+    const char *e = getenv(name);
+    return e && e[0] == '0';
+  }
+};
 
 // Argument check of every jacobi entry point, before anything is launched
 // or captured: the kernels read a 1-cell apron around `region`, and all of
@@ -854,151 +783,6 @@ bool row_extension(const LocalDomain &d, int64_t qi, const Rect3 &region, int mo
   return true;
 }
 
-// shared launch logic: builds params from the domain's CURRENT buffer
-// parity and enqueues the right kernel variant onto `stream`. Also used
-// by the whole-step hipGraph capture (pointers get baked per parity).
-// fullRectVec: 0 = off; 1 = free extension (single-process or RCCL-wire
-// ranks: extended writes land in refresh-before-read halo/slack bytes or
-// exterior cells a later same-stream kernel rewrites); 2 = strict (IPC
-// ranks: a fast peer writes our NEXT-buffer halos during our compute, so
-// no extension is allowed -- the fast path engages only when the region
-// is already aligned, which the allocation pad arranges for the overlap
-// interior).
-// wrap: launch the WRAP instantiation of jacobi_kernel_v4_lds (periodic
-// neighbours read in-kernel): the caller guarantees that `region` is the
-// whole domain and periodic on every axis (see jacobi_graph_create); throws
-// if the LDS kernel would not be selected.
-void launch_jacobi_on(LocalDomain &d, int64_t qi, const Rect3 &region,
-                      const Rect3 &computeRegion, hipStream_t stream, int fullRectVec = 0,
-                      bool wrap = false) {
-  Vec3 ext = region.extent();
-  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return;
-  JacobiParams p{};
-  p.src = d.curr(qi).ptr;
-  p.dst = d.next(qi).ptr;
-  p.pitch = d.curr(qi).pitch;
-  p.plane = d.curr(qi).plane();
-  const Rect3 full = d.full_region();
-  p.allocX = full.lo.x;
-  p.allocY = full.lo.y;
-  p.allocZ = full.lo.z;
-  p.loX = region.lo.x;
-  p.loY = region.lo.y;
-  p.loZ = region.lo.z;
-  p.extX = (int32_t)ext.x;
-  p.extY = (int32_t)ext.y;
-  p.extZ = (int32_t)ext.z;
-  p.cLoX = computeRegion.lo.x;
-  p.cLoY = computeRegion.lo.y;
-  p.cLoZ = computeRegion.lo.z;
-  p.cHiX = computeRegion.hi.x;
-  p.cHiY = computeRegion.hi.y;
-  p.cHiZ = computeRegion.hi.z;
-  // fullRectVec: pure-vector launch over the row-extended region where
-  // row_extension allows it. The extended cells are x-halo cells, cells of
-  // the local rect in the same row (a later same-stream kernel rewrites
-  // them) or pitch-slack bytes: every one is rewritten by the next exchange
-  // (or is padding) before any read, and never a translate SOURCE (sources
-  // are interior cells).
-  int64_t under, over;
-  if (row_extension(d, qi, region, fullRectVec, under, over)) {
-    p.loX = region.lo.x - under;
-    p.extX = (int32_t)(ext.x + under + over);
-    p.vecAll = 1;
-    ext.x = p.extX;
-  }
-  const bool useLds = jac_use_lds();
-  if (wrap && !(p.vecAll && useLds))
-    throw std::runtime_error("jacobi: wrap launch needs the vecAll LDS kernel");
-  if (p.vecAll && useLds && ext.x >= 8) {
-    // LDS-staged y-rows variant (fixed 64x4 block); see jacobi_kernel_v4_lds
-    static int zc = 0;
-    if (!zc) {
-      const char *e = getenv("STENCIL_JAC_ZC");
-      zc = (e && atoi(e) == 16) ? 16 : 32; // 32 measured +1.8% (gpu35)
-    }
-    dim3 block(64, 4, 1);
-    dim3 grid((uint32_t)((p.extX / 4 + 63) / 64), (uint32_t)((ext.y + 3) / 4),
-              (uint32_t)((ext.z + zc - 1) / zc));
-    if (wrap) {
-      JacobiWrapParams wp{};
-      static_cast<JacobiParams &>(wp) = p;
-      wp.trueLoX = region.lo.x;
-      wp.trueExtX = (int32_t)region.extent().x;
-      if (zc == 32)
-        hipLaunchKernelGGL((jacobi_kernel_v4_lds<32, true>), grid, block, 0, stream, wp);
-      else
-        hipLaunchKernelGGL((jacobi_kernel_v4_lds<16, true>), grid, block, 0, stream, wp);
-    } else if (zc == 32)
-      hipLaunchKernelGGL(jacobi_kernel_v4_lds<32>, grid, block, 0, stream, p);
-    else
-      hipLaunchKernelGGL(jacobi_kernel_v4_lds<16>, grid, block, 0, stream, p);
-    STENCIL_HIP(hipGetLastError());
-    return;
-  }
-  if (ext.x >= 8 && ext.y <= 0x7fffffff) {
-    // vectorized row-mapped kernel; block shape tunable via env
-    const int64_t a0 = p.loX - full.lo.x;
-    const int64_t headAl =
-        (int64_t)((16 - (((uintptr_t)p.src + (uintptr_t)(a0 * 4)) & 15)) & 15) >> 2;
-    const int64_t head = p.vecAll ? 0 : std::min<int64_t>(headAl, ext.x);
-    const int64_t units = (ext.x - head) / 4 + (p.vecAll ? 0 : 2);
-    static int bx = 0, by = 0;
-    if (!bx) {
-      bx = 64;
-      by = 4;
-      if (const char *e = getenv("STENCIL_JAC_BLOCK")) {
-        if (sscanf(e, "%dx%d", &bx, &by) != 2 || bx * by != 256) {
-          bx = 64;
-          by = 4;
-        }
-      }
-    }
-    dim3 block((uint32_t)bx, (uint32_t)by, 1);
-    dim3 grid((uint32_t)((units + bx - 1) / bx), (uint32_t)((ext.y + by - 1) / by),
-              (uint32_t)((ext.z + 15) / 16)); // 16 == JAC_ZCHUNK
-    hipLaunchKernelGGL(jacobi_kernel_v4, grid, block, 0, stream, p);
-  } else {
-    hipLaunchKernelGGL(jacobi_kernel, dim3(grid_for(ext.flatten(), 256)), dim3(256), 0,
-                       stream, p);
-  }
-  STENCIL_HIP(hipGetLastError());
-}
-
-} // namespace
-
-void jacobi_step(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                 const Rect3 &computeRegion, int streamId, int extendVec) {
-  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, "jacobi_step");
-  check_jacobi_region(d, region, "jacobi_step");
-  if (extendVec < 0 || extendVec > 2)
-    throw std::invalid_argument("jacobi_step: extend_vec must be 0, 1 or 2");
-  STENCIL_HIP(hipSetDevice(d.gpu()));
-  launch_jacobi_on(d, qi, region, computeRegion, eng.compute_stream(dom, streamId),
-                   extendVec);
-}
-
-namespace {
-
-// The wrap-reading graph serves exactly the single-domain fully periodic
-// whole-domain step that launch_jacobi_on would give to
-// jacobi_kernel_v4_lds. STENCIL_JAC_WRAP=0 forces the translate graph (the
-// A/B lever and the fallback); it is read at each graph creation, which is
-// set-up and never on the step path.
-bool jacobi_wrap_eligible(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                          const Rect3 &computeRegion) {
-  const char *e = getenv("STENCIL_JAC_WRAP");
-  if (e && e[0] == '0') return false;
-  if (dom != 0 || !eng.self_wrap_only(qi, 0)) return false;
-  const LocalDomain &d = eng.domain(dom);
-  if (d.elem_size(qi) != 4) return false;
-  if (!(region == d.compute_region()) || !(region == computeRegion)) return false;
-  // the wrap kernel is a vecAll launch: rows that cannot be extended
-  // (row_extension) fall back to the translate graph
-  int64_t under, over;
-  return jac_use_lds() && row_extension(d, qi, region, /*mode=*/1, under, over);
-}
-
 // Rows per block of jacobi_kernel_fuse2 (6 of them useful). 8 rows are 8
 // waves and 36 KB of LDS, so three blocks share a CU (two while the kernel
 // held 122 VGPRs) and the others compute while one waits at its barrier; 14
@@ -1006,48 +790,39 @@ bool jacobi_wrap_eligible(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 
 // per CU) measured 12% slower at 122 VGPRs.
 constexpr int JAC_F2_NY = 8;
 
-// planes per block of the fused kernel; STENCIL_JAC_F2ZC overrides (read once)
-int jac_f2_zc() {
-  static int zc = 0;
-  if (!zc) {
-    const char *e = getenv("STENCIL_JAC_F2ZC");
-    const int v = e ? atoi(e) : 0;
-    zc = v >= 1 ? v : 64;
-  }
-  return zc;
-}
+// One kernel launch, decided and parameterised: which kernel, its kernargs
+// from the domain's CURRENT buffer parity (raw pointers: the whole-step
+// graphs plan once and bake the pointers per parity, enqueue_current) and its
+// launch shape.
+struct JacobiLaunch {
+  // None: nothing to launch (an empty region, or a Want that cannot be served)
+  enum Kind { None, Scalar, Vec4, Lds, LdsWrap, Fuse2 };
+  // Step: one step of any region. WrapStep / FusedPair: one / two steps of a
+  // whole domain that is periodic on every axis, neighbours read from the far
+  // side of the buffer (the caller vouches for the geometry); only ever the
+  // LdsWrap / Fuse2 kernel.
+  enum Want { Step, WrapStep, FusedPair };
+  Kind kind = None;
+  JacobiWrapParams p{}; // the non-wrap kernels take its JacobiParams base
+  dim3 grid, block;
+  int zc = 0; // planes per block, where it is a template argument (Lds, LdsWrap)
+};
 
-dim3 jac_f2_grid(int64_t extXvec, int64_t extY, int64_t extZ) {
-  const int zc = jac_f2_zc(), ny = JAC_F2_NY;
-  return dim3((uint32_t)((extXvec / 4 + 63) / 64), (uint32_t)((extY + ny - 3) / (ny - 2)),
-              (uint32_t)((extZ + zc - 1) / zc));
-}
-
-// Whether a wrap graph may replay the fused two-step kernel. The kernel
-// serves every geometry the WRAP kernel serves (the wraps are true modulos),
-// so what remains is the switch and the grid limits. STENCIL_JAC_FUSE2=0
-// forces single-step replays (the A/B lever); read at each graph creation.
-bool jacobi_fuse2_eligible(bool wrap, const LocalDomain &d, int64_t qi, const Rect3 &region) {
-  if (!wrap) return false;
-  const char *e = getenv("STENCIL_JAC_FUSE2");
-  if (e && e[0] == '0') return false;
-  int64_t under, over;
-  if (!row_extension(d, qi, region, /*mode=*/1, under, over)) return false;
+// mode: 0 = no row extension; 1 = free extension (single-process or RCCL-wire
+// ranks: extended writes land in refresh-before-read halo/slack bytes or
+// exterior cells a later same-stream kernel rewrites, never in a translate
+// SOURCE, which is an interior cell); 2 = strict (IPC ranks: a fast peer
+// writes our NEXT-buffer halos during our compute, so no extension is allowed
+// -- the fast path engages only when the region is already aligned, which the
+// allocation pad arranges for the overlap interior).
+JacobiLaunch plan_jacobi(const LocalDomain &d, int64_t qi, const Rect3 &region,
+                         const Rect3 &computeRegion, int mode,
+                         JacobiLaunch::Want want = JacobiLaunch::Step) {
+  JacobiLaunch l;
   const Vec3 ext = region.extent();
-  const dim3 g = jac_f2_grid(ext.x + under + over, ext.y, ext.z);
-  // the kernel's lane offsets are 32-bit and stay below one plane stride
-  if (d.curr(qi).plane() > 0x7fffffff) return false;
-  return g.y <= 65535 && g.z <= 65535;
-}
-
-// the fused kernel over the whole (row-extended) domain, curr -> next
-void launch_jacobi_fuse2_on(LocalDomain &d, int64_t qi, const Rect3 &region,
-                            const Rect3 &computeRegion, hipStream_t stream) {
-  const Vec3 ext = region.extent();
-  int64_t under, over;
-  if (!row_extension(d, qi, region, /*mode=*/1, under, over))
-    throw std::runtime_error("jacobi: fused launch needs the row extension");
-  JacobiWrapParams p{};
+  if (ext.x <= 0 || ext.y <= 0 || ext.z <= 0) return l;
+  const JacobiTuning &t = JacobiTuning::get();
+  JacobiWrapParams &p = l.p;
   p.src = d.curr(qi).ptr;
   p.dst = d.next(qi).ptr;
   p.pitch = d.curr(qi).pitch;
@@ -1056,27 +831,151 @@ void launch_jacobi_fuse2_on(LocalDomain &d, int64_t qi, const Rect3 &region,
   p.allocX = full.lo.x;
   p.allocY = full.lo.y;
   p.allocZ = full.lo.z;
-  p.loX = region.lo.x - under;
+  p.loX = p.trueLoX = region.lo.x;
   p.loY = region.lo.y;
   p.loZ = region.lo.z;
-  p.extX = (int32_t)(ext.x + under + over);
+  p.extX = p.trueExtX = (int32_t)ext.x;
   p.extY = (int32_t)ext.y;
   p.extZ = (int32_t)ext.z;
-  p.vecAll = 1;
   p.cLoX = computeRegion.lo.x;
   p.cLoY = computeRegion.lo.y;
   p.cLoZ = computeRegion.lo.z;
   p.cHiX = computeRegion.hi.x;
   p.cHiY = computeRegion.hi.y;
   p.cHiZ = computeRegion.hi.z;
-  p.trueLoX = region.lo.x;
-  p.trueExtX = (int32_t)ext.x;
-  const dim3 grid = jac_f2_grid(p.extX, ext.y, ext.z);
-  hipLaunchKernelGGL(jacobi_kernel_fuse2<JAC_F2_NY>, grid, dim3(64, JAC_F2_NY, 1), 0, stream, p);
+  // pure-vector launch over the row-extended region (at least 8 cells wide)
+  int64_t under, over;
+  if (row_extension(d, qi, region, mode, under, over)) {
+    p.loX -= under;
+    p.extX += (int32_t)(under + over);
+    p.vecAll = 1;
+  }
+  const uint32_t gridX = (uint32_t)((p.extX / 4 + 63) / 64); // 64 vectors per block row
+  const bool lds = p.vecAll && t.lds;
+  // LDS-staged y-rows variant (fixed 64x4 block); see jacobi_kernel_v4_lds
+  auto lds_kernel = [&](JacobiLaunch::Kind kind) {
+    l.kind = kind;
+    l.zc = t.zc;
+    l.block = dim3(64, 4, 1);
+    l.grid = dim3(gridX, (uint32_t)((ext.y + 3) / 4), (uint32_t)((ext.z + t.zc - 1) / t.zc));
+  };
+  switch (want) {
+  case JacobiLaunch::WrapStep:
+    // a row that cannot be extended falls back to the translate graph
+    if (lds && JacobiTuning::wrap()) lds_kernel(JacobiLaunch::LdsWrap);
+    break;
+  case JacobiLaunch::FusedPair: {
+    // the fused kernel serves every geometry the WRAP kernel serves (the
+    // wraps are true modulos); what remains are the grid limits and its
+    // 32-bit lane offsets, which stay below one plane stride
+    const int ny = JAC_F2_NY;
+    l.block = dim3(64, ny, 1);
+    l.grid = dim3(gridX, (uint32_t)((ext.y + ny - 3) / (ny - 2)),
+                  (uint32_t)((ext.z + t.f2zc - 1) / t.f2zc));
+    if (lds && JacobiTuning::wrap() && JacobiTuning::fuse2() && p.plane <= 0x7fffffff &&
+        l.grid.y <= 65535 && l.grid.z <= 65535)
+      l.kind = JacobiLaunch::Fuse2;
+    break;
+  }
+  case JacobiLaunch::Step:
+    if (lds) {
+      lds_kernel(JacobiLaunch::Lds);
+    } else if (p.extX >= 8 && ext.y <= 0x7fffffff) {
+      // vectorized row-mapped kernel: the units formula must match the
+      // kernel's head / body4 / tail
+      const int64_t a0 = p.loX - full.lo.x;
+      const int64_t headAl =
+          (int64_t)((16 - (((uintptr_t)p.src + (uintptr_t)(a0 * 4)) & 15)) & 15) >> 2;
+      const int64_t head = p.vecAll ? 0 : std::min<int64_t>(headAl, p.extX);
+      const int64_t units = (p.extX - head) / 4 + (p.vecAll ? 0 : 2);
+      l.kind = JacobiLaunch::Vec4;
+      l.block = dim3((uint32_t)t.bx, (uint32_t)t.by, 1);
+      l.grid = dim3((uint32_t)((units + t.bx - 1) / t.bx), (uint32_t)((ext.y + t.by - 1) / t.by),
+                    (uint32_t)((ext.z + JAC_ZCHUNK - 1) / JAC_ZCHUNK));
+    } else {
+      // linearized, grid-stride with a capped grid
+      l.kind = JacobiLaunch::Scalar;
+      l.block = dim3(256);
+      l.grid = dim3(grid_for(ext.flatten(), 256));
+    }
+    break;
+  }
+  return l;
+}
+
+void enqueue(const JacobiLaunch &l, hipStream_t stream) {
+  const JacobiParams &base = l.p;
+  switch (l.kind) {
+  case JacobiLaunch::None:
+    return;
+  case JacobiLaunch::Scalar:
+    hipLaunchKernelGGL(jacobi_kernel, l.grid, l.block, 0, stream, base);
+    break;
+  case JacobiLaunch::Vec4:
+    hipLaunchKernelGGL(jacobi_kernel_v4, l.grid, l.block, 0, stream, base);
+    break;
+  case JacobiLaunch::Lds:
+    if (l.zc == 32)
+      hipLaunchKernelGGL(jacobi_kernel_v4_lds<32>, l.grid, l.block, 0, stream, base);
+    else
+      hipLaunchKernelGGL(jacobi_kernel_v4_lds<16>, l.grid, l.block, 0, stream, base);
+    break;
+  case JacobiLaunch::LdsWrap:
+    if (l.zc == 32)
+      hipLaunchKernelGGL((jacobi_kernel_v4_lds<32, true>), l.grid, l.block, 0, stream, l.p);
+    else
+      hipLaunchKernelGGL((jacobi_kernel_v4_lds<16, true>), l.grid, l.block, 0, stream, l.p);
+    break;
+  case JacobiLaunch::Fuse2:
+    hipLaunchKernelGGL(jacobi_kernel_fuse2<JAC_F2_NY>, l.grid, l.block, 0, stream, l.p);
+    break;
+  }
   STENCIL_HIP(hipGetLastError());
 }
 
+// a plan made on either buffer parity, launched on the CURRENT one: only the
+// two pointers differ (same pad and alignment, see row_extension)
+void enqueue_current(JacobiLaunch l, const LocalDomain &d, int64_t qi, hipStream_t stream) {
+  l.p.src = d.curr(qi).ptr;
+  l.p.dst = d.next(qi).ptr;
+  enqueue(l, stream);
+}
+
+// jacobi_step's argument checks, then its plan
+JacobiLaunch checked_step_plan(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                               const Rect3 &computeRegion, int extendVec, const char *name) {
+  LocalDomain &d = checked_jacobi_domain(eng, dom, qi, name);
+  check_jacobi_region(d, region, name);
+  if (extendVec < 0 || extendVec > 2)
+    throw std::invalid_argument(std::string(name) + ": extend_vec must be 0, 1 or 2");
+  return plan_jacobi(d, qi, region, computeRegion, extendVec);
+}
+
 } // namespace
+
+void jacobi_step(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                 const Rect3 &computeRegion, int streamId, int extendVec) {
+  const JacobiLaunch l =
+      checked_step_plan(eng, dom, qi, region, computeRegion, extendVec, "jacobi_step");
+  STENCIL_HIP(hipSetDevice(eng.domain(dom).gpu()));
+  enqueue(l, eng.compute_stream(dom, streamId));
+}
+
+const char *jacobi_step_kernel(ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
+                               const Rect3 &computeRegion, int extendVec) {
+  const JacobiLaunch l =
+      checked_step_plan(eng, dom, qi, region, computeRegion, extendVec, "jacobi_step_kernel");
+  switch (l.kind) {
+  case JacobiLaunch::Scalar:
+    return "scalar";
+  case JacobiLaunch::Vec4:
+    return l.p.vecAll ? "vec4-all" : "vec4";
+  case JacobiLaunch::Lds:
+    return "lds";
+  default:
+    return "none"; // an empty region
+  }
+}
 
 std::unique_ptr<JacobiStepGraph> jacobi_graph_create(ExchangeEngine &eng, int dom, int64_t qi,
                                                      const Rect3 &region,
@@ -1095,13 +994,13 @@ JacobiStepGraph::JacobiStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const
                                  const Rect3 &computeRegion)
     : ReplayGraph(eng, dom) {
   // whole-step replay graph: [translate copy_batch -> boundary fill (if
-  // any axis is non-periodic) -> full-region jacobi -> device-side table swap] captured once per buffer parity. Replay
-  // costs one hipGraphLaunch (~5 us) instead of the ~0.25 ms of host
+  // any axis is non-periodic) -> full-region jacobi -> device-side table
+  // swap] captured once per buffer parity. Replay costs one hipGraphLaunch (~5 us) instead of the ~0.25 ms of host
   // orchestration measured per step at 750^3 (exchange + launches +
   // stream syncs + swap upload). Single-process single-domain only (the
   // periodic self-wrap bench shape): no wire/IPC machinery may exist.
   //
-  // Fully periodic single domain (jacobi_wrap_eligible): every halo cell
+  // Fully periodic single domain (a WrapStep plan exists): every halo cell
   // is a copy of an interior cell of the same buffer, so the graph is the
   // WRAP stencil kernel ALONE -- it reads the wrapped neighbour itself, no
   // translate fills a halo (59 us/step of strided face copies at 750^3)
@@ -1110,12 +1009,22 @@ JacobiStepGraph::JacobiStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const
   // Halos are STALE after steps taken on this path until the next
   // exchange(); interior cells are exact.
   LocalDomain &d = domain();
-  wrap_ = jacobi_wrap_eligible(eng, dom, qi, region, computeRegion);
+  // the wrap kernels serve exactly the single-domain fully periodic
+  // whole-domain step
+  const bool selfPeriodic = dom == 0 && eng.self_wrap_only(qi, 0) && d.elem_size(qi) == 4 &&
+                            region == d.compute_region() && region == computeRegion;
+  // planned once (the levers are read here, at graph creation); the captures
+  // bake the pointers of their parity
+  auto plan = [&](JacobiLaunch::Want want) {
+    return plan_jacobi(d, qi, region, computeRegion, /*mode=*/1, want);
+  };
+  JacobiLaunch step = selfPeriodic ? plan(JacobiLaunch::WrapStep) : JacobiLaunch();
+  wrap_ = step.kind == JacobiLaunch::LdsWrap;
+  if (!wrap_) step = plan(JacobiLaunch::Step);
   for (int par = 0; par < 2; ++par) {
     exec_[par] = capture([&] {
       if (wrap_) {
-        launch_jacobi_on(d, qi, region, computeRegion, stream_, /*fullRectVec=*/1,
-                         /*wrap=*/true);
+        enqueue_current(step, d, qi, stream_);
       } else {
         eng.launch_translates_plain_on((uintptr_t)stream_, 0);
         // physical boundaries (no-op on a fully periodic domain): the fill
@@ -1123,7 +1032,7 @@ JacobiStepGraph::JacobiStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const
         eng.launch_boundary_plain_on((uintptr_t)stream_, 0);
         // the graph's region is the whole interior rect: pure-vector launch
         // (scalar tail lanes measured ~10% of the kernel in the probe)
-        launch_jacobi_on(d, qi, region, computeRegion, stream_, /*fullRectVec=*/1);
+        enqueue_current(step, d, qi, stream_);
         d.enqueue_table_swap(stream_);
       }
     });
@@ -1131,15 +1040,16 @@ JacobiStepGraph::JacobiStepGraph(ExchangeEngine &eng, int dom, int64_t qi, const
   }
   // two swaps: host+device state is back where it started
   //
-  // Fused pairs (jacobi_fuse2_eligible): a second graph per parity holds
-  // jacobi_kernel_fuse2 alone, curr(t) -> next(t+2). A replay of it is ONE
-  // buffer swap like a single step, so after it the buffer that was `next`
-  // is current and holds t+2, while the new `next` still holds time t (not
-  // t+1, which never reaches memory).
-  fused2_ = jacobi_fuse2_eligible(wrap_, d, qi, region);
+  // Fused pairs (a wrap graph with a FusedPair plan): a second graph per
+  // parity holds jacobi_kernel_fuse2 alone, curr(t) -> next(t+2). A replay of
+  // it is ONE buffer swap like a single step, so after it the buffer that was
+  // `next` is current and holds t+2, while the new `next` still holds time t
+  // (not t+1, which never reaches memory).
+  const JacobiLaunch pair = wrap_ ? plan(JacobiLaunch::FusedPair) : JacobiLaunch();
+  fused2_ = pair.kind == JacobiLaunch::Fuse2;
   if (fused2_) {
     for (int par = 0; par < 2; ++par) {
-      exec2_[par] = capture([&] { launch_jacobi_fuse2_on(d, qi, region, computeRegion, stream_); });
+      exec2_[par] = capture([&] { enqueue_current(pair, d, qi, stream_); });
       d.swap();
     }
   }
@@ -1195,18 +1105,21 @@ JacobiMrStepGraph::JacobiMrStepGraph(ExchangeEngine &eng, int dom, int64_t qi,
                                      const std::vector<Rect3> &exteriors, int extendVec)
     : ReplayGraph(eng, dom) {
   LocalDomain &d = domain();
+  const JacobiLaunch inner = plan_jacobi(d, qi, interior, computeRegion, extendVec);
+  std::vector<JacobiLaunch> slabs;
+  for (const Rect3 &box : exteriors)
+    slabs.push_back(plan_jacobi(d, qi, box, computeRegion, /*mode=*/0));
   for (int par = 0; par < 2; ++par) {
     // A: interior + outgoing halos
     execA_[par] = capture([&] {
-      launch_jacobi_on(d, qi, interior, computeRegion, stream_, extendVec);
+      enqueue_current(inner, d, qi, stream_);
       eng.launch_translates_plain_on((uintptr_t)stream_, 0);
       eng.launch_packs_plain_on((uintptr_t)stream_, 1 + par); // staged parity
     });
     // B: incoming halos + exterior + swap
     execB_[par] = capture([&] {
       eng.launch_unpacks_plain_on((uintptr_t)stream_, 1 + par);
-      for (const Rect3 &box : exteriors)
-        launch_jacobi_on(d, qi, box, computeRegion, stream_, /*fullRectVec=*/0);
+      for (const JacobiLaunch &slab : slabs) enqueue_current(slab, d, qi, stream_);
       d.enqueue_table_swap(stream_);
       eng.enqueue_view_flips((uintptr_t)stream_);
     });

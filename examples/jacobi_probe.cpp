@@ -12,13 +12,16 @@
 #include <cstdlib>
 #include <hip/hip_runtime.h>
 
+#include "stencil_amd/device_util.hpp"
+
+// lane shifts, scalar bases and vfloat4
+using namespace stencil_amd;
+
 #define CHECK(x)                                                                                   \
   if ((x) != hipSuccess) {                                                                         \
     printf("hip error %s @%d\n", hipGetErrorString(hipGetLastError()), __LINE__);                  \
     exit(1);                                                                                       \
   }
-
-typedef float vfloat4 __attribute__((ext_vector_type(4)));
 
 struct P {
   const char *src;
@@ -275,34 +278,6 @@ __global__ void __launch_bounds__(256) probe_prod(P p, const char *const *srcSlo
       }
     }
   }
-}
-
-// lane shifts and scalar bases as in csrc/src/jacobi.hip
-__device__ __forceinline__ float lane_below(float v, float first) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v),
-                                                    0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float lane_above(float v) {
-  const int i = __float_as_int(v);
-  return __int_as_float(__builtin_amdgcn_update_dpp(i, i, 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
-}
-template <int N> __device__ __forceinline__ float row_above(float v) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + N /* row_shl:N */, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float lane_value(float v, int lane) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-typedef __attribute__((address_space(1))) char gchar;
-__device__ __forceinline__ gchar *global_base(const void *p) {
-  const uint64_t v = (uint64_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return (gchar *)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ uint32_t lane_offset(uint32_t o) {
-  asm volatile("" : "+v"(o));
-  return o;
 }
 
 // Two time steps per pass, the tile structure and the code of the production

@@ -219,7 +219,7 @@ class Jacobi3D:
     def _eager_step(self, overlap: bool = True):
         dd = self.dd
         # pure-vector + LDS-rows fast path (see csrc/src/jacobi.hip
-        # launch_jacobi_on). Mode 1 (free row extension) is valid when the
+        # plan_jacobi). Mode 1 (free row extension) is valid when the
         # extended cells are discard-safe LOCALLY: single process, or
         # multi-rank without direct IPC writes (an IPC peer running one
         # exchange ahead writes our next-buffer halos during our compute,

@@ -82,8 +82,22 @@ def _sl(lo, hi, flo):
     return tuple(slice(lo[a] - flo[a], hi[a] - flo[a]) for a in (2, 1, 0))
 
 
+def _rect(lo, hi):
+    return _C.Rect3(_C.Vec3(*lo), _C.Vec3(*hi))
+
+
+def _kind(dom, li, lo, hi, mode):
+    """the kernel jacobi_step picks for this launch (plans, launches nothing)"""
+    return _C.jacobi_step_kernel(dom.dd.backend.engine, li, dom.h.index, _rect(lo, hi),
+                                 _rect((0, 0, 0), dom.size), extend_vec=mode)
+
+
+KINDS = set()  # the kernels of the launches _check_launch has checked in this process
+
+
 def _check_launch(dom, li, lo, hi, mode):
     dd, h = dom.dd, dom.h
+    KINDS.add(_kind(dom, li, lo, hi, mode))
     flo, fhi = dom.full[li]
     field, sent = dom.field[li], dom.sent[li]
     what = f"size {dom.size} r {dd.radius.x(1)} domain {li} region {lo}..{hi} extend_vec={mode}"
@@ -197,6 +211,24 @@ def test_kernel_bits_and_containment(size, radius, n_domains, family):
     assert n >= 3 * n_domains
 
 
+def test_kernel_cases_reach_every_kernel():
+    """the launches of KERNEL_CASES, planned again without launching: every
+    kernel a default process can pick is among them, and nothing
+    _check_launch has met so far is missing from the plan. (Planned again
+    rather than read from KINDS alone, so that the answer does not depend on
+    which tests ran before this one; the planner is the one jacobi_step
+    launches from.)"""
+    kinds = set()
+    for size, radius, n_domains, families in KERNEL_CASES:
+        dom = _dom(size, radius, n_domains)
+        for li in range(n_domains):
+            for fam in families:
+                for lo, hi in _regions(dom, li, fam):
+                    kinds.update(_kind(dom, li, lo, hi, mode) for mode in MODES)
+    assert kinds >= {"scalar", "vec4", "lds"}
+    assert KINDS <= kinds
+
+
 def test_zero_slack_rows_really_have_none():
     """(62,5,3) at radius 1 and (60,5,3) at radius 2 are 64 cells per row:
     exactly one 256 B pitch"""
@@ -218,6 +250,7 @@ for size, radius in (((19, 10, 9), 1), ((62, 5, 3), 1)):
                 t._check_launch(dom, 0, lo, hi, mode)
                 n += 1
 print("lds-off cases ok:", n)
+print("lds-off kinds:", sorted(t.KINDS))
 """
 
 
@@ -234,6 +267,8 @@ def test_kernel_bits_with_the_lds_kernel_off():
                          text=True, timeout=120)
     assert res.returncode == 0, res.stdout + res.stderr
     assert "lds-off cases ok: 12" in res.stdout, res.stdout + res.stderr
+    kinds = res.stdout.split("lds-off kinds:")[1].splitlines()[0]
+    assert "'vec4-all'" in kinds and "'lds'" not in kinds, res.stdout
 
 
 def test_validation_launches_nothing():
