@@ -109,7 +109,7 @@ inline void check_inside(const char *op, const char *what, const Rect3 &r,
 // The region's first cell in every operand's buffer, `pos` being the
 // region's lo in allocation coordinates; the buffers share one layout.
 struct RegionCells {
-  static constexpr int kMax = 5;
+  static constexpr int kMax = 6;
   int64_t pitch = 0, plane = 0; // byte strides, the same for every operand
   int n = 0;
   char *ptr[kMax] = {};

@@ -260,9 +260,47 @@ void cg_update_sum_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, 
 void field_axpbyc(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, double beta,
                   int64_t y, bool yNext, double c, int64_t out, bool outNext,
                   const Rect3 &region, int streamId = 0);
+
+// The fused passes of BiCGStab (stencil_amd/solvers/bicgstab.py), the
+// Krylov method for non-symmetric operators. The contract, the walks, the
+// validation and the determinism of the ops above; the launch shapes are
+// theirs too, so a value that an op above also computes has the same bits.
+//
+// out = alpha * x + beta * y as field_axpby writes it, returning sum out^2
+// of the stored (rounded) out, squares and sums in fp64: field_axpby's 3
+// passes, no fourth for the norm. out may be the buffer of x or of y.
+double field_axpby_norm2(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                         double beta, int64_t y, bool yNext, int64_t out, bool outNext,
+                         const Rect3 &region, int streamId = 0);
+void field_axpby_norm2_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                             double beta, int64_t y, bool yNext, int64_t out, bool outNext,
+                             const Rect3 &region, int streamId = 0);
+// (sum a * b, sum a * a) from ONE pass over a and b: field_dot's traffic
+std::array<double, 2> field_dot_pair(ExchangeEngine &eng, int dom, int64_t a, bool aNext,
+                                     int64_t b, bool bNext, const Rect3 &region,
+                                     int streamId = 0);
+void field_dot_pair_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b,
+                          bool bNext, const Rect3 &region, int streamId = 0);
+// the fused BiCGStab update, one pass of 8 (7 when z is the buffer of r)
+// instead of 11:
+//   curr[x] += alpha * y + omega * z;  curr[r] -= omega * t
+// returning (sum r_new^2, sum rhat * r_new), fp64 accumulation of the
+// rounded r_new. On entry curr[r] holds s. alpha and omega are rounded to
+// the quantity's type once. z may be the buffer of r: every cell is read
+// before it is written. curr[x] and curr[r] must be distinct from each
+// other and from the buffers of y, t and rhat (std::invalid_argument).
+std::array<double, 2> bicgstab_update(ExchangeEngine &eng, int dom, double alpha, int64_t y,
+                                      bool yNext, double omega, int64_t z, bool zNext, int64_t x,
+                                      int64_t r, int64_t t, bool tNext, int64_t rhat,
+                                      bool rhatNext, const Rect3 &region, int streamId = 0);
+void bicgstab_update_begin(ExchangeEngine &eng, int dom, double alpha, int64_t y, bool yNext,
+                           double omega, int64_t z, bool zNext, int64_t x, int64_t r, int64_t t,
+                           bool tNext, int64_t rhat, bool rhatNext, const Rect3 &region,
+                           int streamId = 0);
+
 // wait for the n-valued reduction begun on `dom` and write its values to
 // out[0..n): n = 1 field_sum (and the one-valued ops above), 2
-// cg_update_sum, 3 field_dot_sums. std::runtime_error, the reduction
+// cg_update_sum, field_dot_pair and bicgstab_update, 3 field_dot_sums. std::runtime_error, the reduction
 // staying in flight, when the one in flight has another value count;
 // std::invalid_argument for n outside 1..kReduceValues or a null out.
 void reduction_end_n(ExchangeEngine &eng, int dom, double *out, int n);

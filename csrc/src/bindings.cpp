@@ -589,6 +589,85 @@ PYBIND11_MODULE(_C, m) {
       py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
       py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("c"), py::arg("out"),
       py::arg("out_next"), py::arg("region"), py::arg("stream_id") = 0);
+  // the fused passes of BiCGStab
+  m.def(
+      "field_axpby_norm2",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                     double beta, int64_t y, bool yNext, int64_t out, bool outNext,
+                     const Rect3 &region, int streamId) {
+        return value_errors([&] {
+          return field_axpby_norm2(eng, dom, alpha, x, xNext, beta, y, yNext, out, outNext, region,
+                                   streamId);
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
+      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"), py::arg("out_next"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "field_axpby_norm2_begin",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                     double beta, int64_t y, bool yNext, int64_t out, bool outNext,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_axpby_norm2_begin(eng, dom, alpha, x, xNext, beta, y, yNext, out, outNext, region,
+                                  streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
+      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"), py::arg("out_next"),
+      py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "field_dot_pair",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                     const Rect3 &region, int streamId) {
+        const std::array<double, 2> v = value_errors(
+            [&] { return field_dot_pair(eng, dom, a, aNext, b, bNext, region, streamId); });
+        return py::make_tuple(v[0], v[1]);
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "field_dot_pair_begin",
+      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
+                     const Rect3 &region, int streamId) {
+        value_errors([&] {
+          field_dot_pair_begin(eng, dom, a, aNext, b, bNext, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def(
+      "bicgstab_update",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t y, bool yNext,
+                     double omega, int64_t z, bool zNext, int64_t x, int64_t r, int64_t t,
+                     bool tNext, int64_t rhat, bool rhatNext, const Rect3 &region, int streamId) {
+        const std::array<double, 2> v = value_errors([&] {
+          return bicgstab_update(eng, dom, alpha, y, yNext, omega, z, zNext, x, r, t, tNext, rhat,
+                                 rhatNext, region, streamId);
+        });
+        return py::make_tuple(v[0], v[1]);
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("y"), py::arg("y_next"),
+      py::arg("omega"), py::arg("z"), py::arg("z_next"), py::arg("x"), py::arg("r"), py::arg("t"),
+      py::arg("t_next"), py::arg("rhat"), py::arg("rhat_next"), py::arg("region"),
+      py::arg("stream_id") = 0);
+  m.def(
+      "bicgstab_update_begin",
+      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t y, bool yNext,
+                     double omega, int64_t z, bool zNext, int64_t x, int64_t r, int64_t t,
+                     bool tNext, int64_t rhat, bool rhatNext, const Rect3 &region, int streamId) {
+        value_errors([&] {
+          bicgstab_update_begin(eng, dom, alpha, y, yNext, omega, z, zNext, x, r, t, tNext, rhat,
+                                rhatNext, region, streamId);
+          return 0;
+        });
+      },
+      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("y"), py::arg("y_next"),
+      py::arg("omega"), py::arg("z"), py::arg("z_next"), py::arg("x"), py::arg("r"), py::arg("t"),
+      py::arg("t_next"), py::arg("rhat"), py::arg("rhat_next"), py::arg("region"),
+      py::arg("stream_id") = 0);
   m.def(
       "reduction_end_n",
       [value_errors](ExchangeEngine &eng, int dom, int n) {

@@ -7,6 +7,9 @@
 // sum of a field, the inner product together with both sums, the fused
 // update together with sum r_new, and out = alpha x + beta y + c: the
 // projection v - mean(v) rides on passes the iteration makes anyway.
+// For non-symmetric problems (solvers/bicgstab.py) the three fused passes of
+// a BiCGStab iteration: out = alpha x + beta y with sum out^2, the pair
+// (a . b, a . a), and the update of x and r with (r . r, rhat . r).
 //
 // Contract (the stencil operator's): nothing outside `region` is written
 // in any buffer, and no cell outside it enters the arithmetic. Unlike the
@@ -259,14 +262,101 @@ template <typename T> struct ScaledF {
   }
 };
 
+// The fused passes of BiCGStab (solvers/bicgstab.py).
+//
+// alpha x + beta y with the bits field_axpby writes. AxpbyF leaves the
+// contraction to the compiler, which in field_kernel settles on
+// fma(alpha, x, beta y) for the strips and for double, and on two rounded
+// products and a sum for a float cell (it pairs the products into one
+// packed multiply); tests/golden/vector_ops_bits.json pins that. In a
+// reduction kernel the same expression contracts otherwise (the float cell
+// gets an fma), so the forms are spelled out here.
+__device__ __forceinline__ float axpby_bits(float alpha, float x, float beta, float y) {
+  return __fadd_rn(__fmul_rn(alpha, x), __fmul_rn(beta, y));
+}
+__device__ __forceinline__ double axpby_bits(double alpha, double x, double beta, double y) {
+  return __builtin_fma(alpha, x, __dmul_rn(beta, y));
+}
+__device__ __forceinline__ F4 axpby_bits(float alpha, F4 x, float beta, F4 y) {
+  F4 o;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) o[c] = __builtin_fmaf(alpha, x[c], __fmul_rn(beta, y[c]));
+  return o;
+}
+__device__ __forceinline__ D2 axpby_bits(double alpha, D2 x, double beta, D2 y) {
+  D2 o;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) o[c] = axpby_bits(alpha, x[c], beta, y[c]);
+  return o;
+}
+
+// out = alpha x + beta y; sum out^2, of the out that is stored
+template <typename T> struct AxpbyNormF {
+  static constexpr int NV = 1;
+  const char *x, *y;
+  char *out;
+  T alpha, beta;
+  double acc[NV];
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vx = *(const V *)(x + off), vy = *(const V *)(y + off);
+    const V vo = axpby_bits(alpha, vx, beta, vy);
+    *(V *)(out + off) = vo;
+    add_prod(acc[0], vo, vo);
+  }
+};
+
+// (a . b, a . a)
+struct DotPairF {
+  static constexpr int NV = 2;
+  const char *a, *b;
+  double acc[NV];
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V va = *(const V *)(a + off), vb = *(const V *)(b + off);
+    add_prod(acc[0], va, vb);
+    add_prod(acc[1], va, va);
+  }
+};
+
+// x += alpha y + omega z; r -= omega t; (r_new . r_new, rhat . r_new).
+// z may be the buffer of r (no __restrict__ anywhere): every load of a cell
+// stands before its stores.
+template <typename T> struct BicgF {
+  static constexpr int NV = 2;
+  const char *y, *z;
+  char *x, *r;
+  const char *t, *rhat;
+  T alpha, omega;
+  double acc[NV];
+  template <typename V> __device__ __forceinline__ void at(int64_t off) {
+    const V vy = *(const V *)(y + off), vz = *(const V *)(z + off);
+    const V vt = *(const V *)(t + off), vh = *(const V *)(rhat + off);
+    const V vx = *(const V *)(x + off), vr = *(const V *)(r + off);
+    const V rn = vr - omega * vt;
+    *(V *)(x + off) = vx + alpha * vy + omega * vz;
+    *(V *)(r + off) = rn;
+    add_prod(acc[0], rn, rn);
+    add_prod(acc[1], vh, rn);
+  }
+};
+
 // Waves per SIMD a reduction is held to; 0: the compiler's choice.
 // DotF<true> in float: the 4 x unrolled strip loop wants 74 VGPRs to keep
 // its 8 loads in flight. Held to 64 (8 waves per SIMD) the scheduler
 // serialises them, 2 in flight, and the kernel runs 5-6% behind DotF<false>;
 // at 6 waves it batches them as DotF<false> does. double fits 8 waves as it
 // is.
+// DotPairF in float is the same case with the other outcome of the same
+// pressure: left to the compiler it takes 26 VGPRs and waits after every
+// pair of loads; at 6 waves it takes 72 and keeps the 8 loads in flight
+// (0.24 ms at 512^3, DotF<false>'s time). double batches at 8 waves in 44.
+// AxpbyNormF (32 VGPRs) and BicgF (70 in float, 7 waves; 62 in double) have
+// no entry: their stores may alias the next plane's loads, so a plane's
+// loads (2 and 6) are issued together and waited for before its stores, as
+// in CgF, whatever the budget; they run at the rate of the storing kernels
+// (BASELINE.md "BiCGStab").
 template <typename F, typename T> constexpr int kWaves = 0;
 template <typename T> constexpr int kWaves<DotF<true>, T> = sizeof(T) == 4 ? 6 : 8;
+template <typename T> constexpr int kWaves<DotPairF, T> = sizeof(T) == 4 ? 6 : 8;
 
 template <typename T, bool STRIPS, typename F>
 __global__ void __launch_bounds__(256) field_kernel(Geom g, F f) {
@@ -446,7 +536,76 @@ void check_distinct(const char *op, int64_t x, int64_t p, int64_t r) {
     throw std::invalid_argument(std::string(op) + ": x, p and r must be distinct quantities");
 }
 
+// bicgstab_update writes curr[x] and curr[r]: neither may be the other, nor
+// a buffer the op only reads, except z, which may be r's (every cell is
+// read before it is written)
+void check_distinct_bicg(const char *op, int64_t x, int64_t r, const Operand &y, const Operand &t,
+                         const Operand &rhat) {
+  bool bad = x == r;
+  for (const Operand *o : {&y, &t, &rhat}) bad = bad || (!o->next && (o->q == x || o->q == r));
+  if (bad)
+    throw std::invalid_argument(std::string(op) + ": x and r must be distinct from each other "
+                                                  "and from y, t and rhat");
+}
+
 } // namespace
+
+void field_axpby_norm2_begin(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                             double beta, int64_t y, bool yNext, int64_t out, bool outNext,
+                             const Rect3 &region, int streamId) {
+  begin_reduce("field_axpby_norm2", eng, dom, {{x, xNext}, {y, yNext}, {out, outNext}}, region,
+               streamId, [=](auto t, char *const *p) {
+                 typedef decltype(t) T;
+                 return AxpbyNormF<T>{p[0], p[1], p[2], (T)alpha, (T)beta, {}};
+               });
+}
+
+void field_dot_pair_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b,
+                          bool bNext, const Rect3 &region, int streamId) {
+  begin_reduce("field_dot_pair", eng, dom, {{a, aNext}, {b, bNext}}, region, streamId,
+               [](auto, char *const *p) { return DotPairF{p[0], p[1], {}}; });
+}
+
+// operands: y, z, curr[x], curr[r], t, rhat
+void bicgstab_update_begin(ExchangeEngine &eng, int dom, double alpha, int64_t y, bool yNext,
+                           double omega, int64_t z, bool zNext, int64_t x, int64_t r, int64_t t,
+                           bool tNext, int64_t rhat, bool rhatNext, const Rect3 &region,
+                           int streamId) {
+  check_distinct_bicg("bicgstab_update", x, r, {y, yNext}, {t, tNext}, {rhat, rhatNext});
+  begin_reduce("bicgstab_update", eng, dom,
+               {{y, yNext}, {z, zNext}, {x, false}, {r, false}, {t, tNext}, {rhat, rhatNext}},
+               region, streamId, [=](auto ty, char *const *q) {
+                 typedef decltype(ty) T;
+                 return BicgF<T>{q[0], q[1], q[2], q[3], q[4], q[5], (T)alpha, (T)omega, {}};
+               });
+}
+
+double field_axpby_norm2(ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
+                         double beta, int64_t y, bool yNext, int64_t out, bool outNext,
+                         const Rect3 &region, int streamId) {
+  field_axpby_norm2_begin(eng, dom, alpha, x, xNext, beta, y, yNext, out, outNext, region,
+                          streamId);
+  return reduction_end(eng, dom);
+}
+
+std::array<double, 2> field_dot_pair(ExchangeEngine &eng, int dom, int64_t a, bool aNext,
+                                     int64_t b, bool bNext, const Rect3 &region, int streamId) {
+  field_dot_pair_begin(eng, dom, a, aNext, b, bNext, region, streamId);
+  std::array<double, 2> out{};
+  reduction_end_n(eng, dom, out.data(), 2);
+  return out;
+}
+
+std::array<double, 2> bicgstab_update(ExchangeEngine &eng, int dom, double alpha, int64_t y,
+                                      bool yNext, double omega, int64_t z, bool zNext, int64_t x,
+                                      int64_t r, int64_t t, bool tNext, int64_t rhat,
+                                      bool rhatNext, const Rect3 &region, int streamId) {
+  bicgstab_update_begin(eng, dom, alpha, y, yNext, omega, z, zNext, x, r, t, tNext, rhat,
+                        rhatNext, region, streamId);
+  std::array<double, 2> out{};
+  reduction_end_n(eng, dom, out.data(), 2);
+  return out;
+}
 
 void field_dot_begin(ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
                      const Rect3 &region, int streamId) {

@@ -585,6 +585,43 @@ class DistributedDomain:
         self.backend.field_axpbyc(boxes, float(alpha), qx, nx, float(beta), qy, ny, float(c),
                                   qo, no)
 
+    # The fused passes of BiCGStab (solvers/bicgstab.py). GLOBAL values like
+    # dot(): bitwise identical on every rank.
+    def axpby_norm2(self, alpha: float, x, beta: float, y, out, where="all") -> float:
+        """out = alpha * x + beta * y exactly as axpby() writes it, and the
+        GLOBAL sum of out^2 (the stored out, squares and sums in fp64) from
+        the same pass: 3 passes where axpby + dot take 4. out may be the
+        buffer of x or of y. Blocks until the value is there."""
+        (qx, nx), (qy, ny), (qo, no) = self._vector_operands("axpby_norm2", [x, y, out])
+        boxes = self._vector_boxes("axpby_norm2", where)
+        return self._global_sum(self.backend.field_axpby_norm2(
+            boxes, float(alpha), qx, nx, float(beta), qy, ny, qo, no))
+
+    def dot_pair(self, a, b, where="all"):
+        """(sum a * b, sum a * a), GLOBAL, from ONE pass over a and b:
+        dot()'s traffic, and its first value has dot(a, b)'s bits."""
+        (qa, na), (qb, nb) = self._vector_operands("dot_pair", [a, b])
+        boxes = self._vector_boxes("dot_pair", where)
+        return self._global_sums(self.backend.field_dot_pair(boxes, qa, na, qb, nb), 2)
+
+    def bicgstab_update(self, alpha: float, y, omega: float, z, x, r, t, rhat):
+        """the fused BiCGStab update over every local_rect:
+        curr[x] += alpha * y + omega * z; curr[r] -= omega * t (curr[r]
+        holds s on entry); returns the GLOBAL (sum r_new^2, sum rhat *
+        r_new). x and r are handles; y, z, t and rhat handles or
+        Next(handle). z may be the buffer of r (the unpreconditioned
+        solver: 7 passes, otherwise 8). ValueError when x and r are not
+        distinct from each other and from the buffers of y, t and rhat."""
+        for h in (x, r):
+            if not isinstance(h, DataHandle):
+                raise TypeError("bicgstab_update: x and r are DataHandles")
+        (qy, ny), (qz, nz), (qx, _), (qr, _), (qt, nt), (qh, nh) = self._vector_operands(
+            "bicgstab_update", [y, z, x, r, t, rhat])
+        boxes = self._vector_boxes("bicgstab_update", "all")
+        return self._global_sums(
+            self.backend.bicgstab_update(boxes, float(alpha), qy, ny, float(omega), qz, nz, qx, qr,
+                                         qt, nt, qh, nh), 2)
+
     # ---- geometry queries ----
     def any_methods(self, m: Method) -> bool:
         """True if any of the given transport methods are enabled

@@ -859,6 +859,38 @@ class NativeBackend:
             _C.field_axpbyc(self.engine, li, alpha, x, x_next, beta, y, y_next, c, out, out_next,
                             _rect3(lo, hi), stream_id)
 
+    # ---- the fused passes of BiCGStab ----
+    def field_axpby_norm2(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
+                          y_next: bool, out: int, out_next: bool,
+                          stream_id: int = 0) -> List[float]:
+        """field_axpby per local domain, returning each domain's sum of
+        out^2 from the same pass"""
+        return [v[0] for v in self._reduce_n(
+            boxes, 1,
+            lambda li, rect: _C.field_axpby_norm2_begin(self.engine, li, alpha, x, x_next, beta,
+                                                        y, y_next, out, out_next, rect,
+                                                        stream_id))]
+
+    def field_dot_pair(self, boxes, a: int, a_next: bool, b: int, b_next: bool,
+                       stream_id: int = 0) -> List[tuple]:
+        """per local domain: (sum a * b, sum a * a) over its box from one pass"""
+        return self._reduce_n(
+            boxes, 2,
+            lambda li, rect: _C.field_dot_pair_begin(self.engine, li, a, a_next, b, b_next, rect,
+                                                     stream_id))
+
+    def bicgstab_update(self, boxes, alpha: float, y: int, y_next: bool, omega: float, z: int,
+                        z_next: bool, x: int, r: int, t: int, t_next: bool, rhat: int,
+                        rhat_next: bool, stream_id: int = 0) -> List[tuple]:
+        """fused BiCGStab update per local domain: curr[x] += alpha * y +
+        omega * z; curr[r] -= omega * t; returns each domain's
+        (sum r_new^2, sum rhat * r_new)"""
+        return self._reduce_n(
+            boxes, 2,
+            lambda li, rect: _C.bicgstab_update_begin(self.engine, li, alpha, y, y_next, omega, z,
+                                                      z_next, x, r, t, t_next, rhat, rhat_next,
+                                                      rect, stream_id))
+
     def jacobi_graph_create(self, li: int, qi: int, region_lo: Vec, region_hi: Vec,
                             c_lo: Vec, c_hi: Vec) -> "_C.JacobiStepGraph":
         """whole-step replay graph (single-process single-domain path);

@@ -20,6 +20,9 @@ stream of the given ExchangeEngine; regions are global-coordinate Rect3s.
   the projection off the constant null space needs, fused into the passes
   of field_dot, cg_update and field_axpby; their *_begin forms end with
   reduction_end_n
+- field_axpby_norm2 / field_dot_pair / bicgstab_update: the three fused
+  passes of a BiCGStab iteration (non-symmetric operators); their *_begin
+  forms end with reduction_end / reduction_end_n
 - diffusion_apply / diffusion_inv_diagonal: the variable-coefficient
   operator sigma I - div(k grad) and omega over its diagonal
   (csrc/src/diffusion_op.hip)
@@ -29,6 +32,8 @@ from .._C import (  # noqa: F401
     MhdCoeffs,
     StencilTaps,
     StencilType,
+    bicgstab_update,
+    bicgstab_update_begin,
     cg_update,
     cg_update_begin,
     cg_update_sum,
@@ -36,9 +41,13 @@ from .._C import (  # noqa: F401
     diffusion_apply,
     diffusion_inv_diagonal,
     field_axpby,
+    field_axpby_norm2,
+    field_axpby_norm2_begin,
     field_axpbyc,
     field_dot,
     field_dot_begin,
+    field_dot_pair,
+    field_dot_pair_begin,
     field_dot_sums,
     field_dot_sums_begin,
     field_scaled_update,
@@ -60,6 +69,8 @@ __all__ = [
     "MhdCoeffs",
     "StencilTaps",
     "StencilType",
+    "bicgstab_update",
+    "bicgstab_update_begin",
     "cg_update",
     "cg_update_begin",
     "cg_update_sum",
@@ -67,9 +78,13 @@ __all__ = [
     "diffusion_apply",
     "diffusion_inv_diagonal",
     "field_axpby",
+    "field_axpby_norm2",
+    "field_axpby_norm2_begin",
     "field_axpbyc",
     "field_dot",
     "field_dot_begin",
+    "field_dot_pair",
+    "field_dot_pair_begin",
     "field_dot_sums",
     "field_dot_sums_begin",
     "field_scaled_update",

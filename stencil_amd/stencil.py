@@ -116,6 +116,48 @@ class Stencil:
         return cls.star(*axes)
 
     @classmethod
+    def advection(cls, velocity: Sequence[float], spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                  scheme: str = "upwind") -> "Stencil":
+        """v . grad for a constant velocity on a grid with per-axis
+        `spacing`. "upwind" is first order and reads only against the flow:
+        per axis v_a (u_i - u_{i-1}) / h_a for v_a > 0, v_a (u_{i+1} - u_i)
+        / h_a for v_a < 0, so radius() allocates no downwind halo.
+        "central" is v_a (u_{i+1} - u_{i-1}) / (2 h_a). An axis with
+        v_a == 0 gets no tap. ValueError for a non-finite velocity, a zero
+        velocity on every axis and an unknown scheme."""
+        if scheme not in ("upwind", "central"):
+            raise ValueError(f"advection scheme is 'upwind' or 'central', got {scheme!r}")
+        if len(velocity) != 3 or any(not math.isfinite(float(v)) for v in velocity):
+            raise ValueError(f"velocity must be three finite numbers, got {velocity!r}")
+        if all(float(v) == 0.0 for v in velocity):
+            raise ValueError("advection(): the velocity is zero on every axis")
+        if len(spacing) != 3 or any(not (float(h) > 0 and math.isfinite(float(h))) for h in spacing):
+            raise ValueError(f"spacing must be three positive finite numbers, got {spacing!r}")
+        offsets: List[Offset] = []
+        weights: List[float] = []
+
+        def tap(axis, k, w):
+            o = [0, 0, 0]
+            o[axis] = k
+            offsets.append(tuple(o))
+            weights.append(w)
+
+        for a, (v, h) in enumerate(zip(velocity, spacing)):
+            v, h = float(v), float(h)
+            if v == 0.0:
+                continue
+            if scheme == "central":
+                tap(a, 1, v / (2.0 * h))
+                tap(a, -1, -v / (2.0 * h))
+            elif v > 0.0:
+                tap(a, 0, v / h)
+                tap(a, -1, -v / h)
+            else:
+                tap(a, 1, v / h)
+                tap(a, 0, -v / h)
+        return cls(offsets, weights)
+
+    @classmethod
     def from_array(cls, kernel_zyx, center: Sequence[int]) -> "Stencil":
         """dense box: kernel_zyx[k][j][i] weighs offset (i - cx, j - cy,
         k - cz) with center = (cx, cy, cz)"""
@@ -188,6 +230,18 @@ class Stencil:
         return all(
             self._taps.get((-o[0], -o[1], -o[2])) == w for o, w in self._taps.items()
         )
+
+    def symmetric_part(self) -> "Stencil":
+        """the stencil with weights (w(o) + w(-o)) / 2: on a periodic grid
+        the symmetric part (A + A^T) / 2 of the operator. For a first-order
+        upwind advection it is -(|v_a| h_a / 2) times the second difference
+        per axis, the scheme's numerical diffusion. ValueError when nothing
+        is left (a skew stencil such as the central advection)."""
+        offs = set(self._taps) | {(-o[0], -o[1], -o[2]) for o in self._taps}
+        offs = sorted(offs, key=lambda o: (o[2], o[1], o[0]))
+        return Stencil(offs, [
+            (self._taps.get(o, 0.0) + self._taps.get((-o[0], -o[1], -o[2]), 0.0)) / 2.0
+            for o in offs])
 
     def radius(self) -> "_C.Radius":
         """minimal Radius that makes every read legal. Face radii are the

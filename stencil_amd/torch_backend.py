@@ -626,5 +626,56 @@ class TorchBackend:
                           for s in (alpha, beta, c))
             tout.copy_(al * tx + be * ty + cc)
 
+    # ---- the fused passes of BiCGStab (vector_ops.hip's third family) ----
+    def field_axpby_norm2(self, boxes, alpha, x, x_next, beta, y, y_next, out, out_next,
+                          stream_id=0):
+        """field_axpby, returning each domain's sum of out^2 (the stored
+        out, squares and sums in fp64)"""
+        self.field_axpby(boxes, alpha, x, x_next, beta, y, y_next, out, out_next)
+        return self.field_dot(boxes, out, out_next, out, out_next)
+
+    def field_dot_pair(self, boxes, a, a_next, b, b_next, stream_id=0):
+        """per local domain: (sum a * b, sum a * a) over its box, in fp64"""
+        res = []
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views("field_dot_pair", li, lo, hi, [(a, a_next), (b, b_next)])
+            if v is None:
+                res.append((0.0, 0.0))
+                continue
+            ta, tb = v[0].double(), v[1].double()
+            res.append((float((ta * tb).sum()), float((ta * ta).sum())))
+        return res
+
+    def bicgstab_update(self, boxes, alpha, y, y_next, omega, z, z_next, x, r, t, t_next, rhat,
+                        rhat_next, stream_id=0):
+        """x = x + alpha y + omega z; r = r - omega t, in the quantity's
+        type with alpha and omega rounded to it once, every operand read
+        before x and r are written (z may be the buffer of r); returns each
+        domain's (dot(r, r), dot(rhat, r))"""
+        op = "bicgstab_update"
+        reads = [(y, y_next), (t, t_next), (rhat, rhat_next)]
+        if x == r or any(not nxt and q in (x, r) for q, nxt in reads):
+            raise ValueError(f"{op}: x and r must be distinct from each other and from y, t "
+                             "and rhat")
+        operands = [(y, y_next), (z, z_next), (x, False), (r, False), (t, t_next),
+                    (rhat, rhat_next)]
+        views = [self._vector_views(op, li, lo, hi, operands)
+                 for li, (lo, hi) in enumerate(boxes)]  # validate before any write
+        res = []
+        for v in views:
+            if v is None:
+                res.append((0.0, 0.0))
+                continue
+            ty, tz, tx, tr, tt, th = v
+            al = torch.tensor(alpha, dtype=tx.dtype, device=tx.device)
+            om = torch.tensor(omega, dtype=tx.dtype, device=tx.device)
+            xn = tx + al * ty + om * tz
+            rn = tr - om * tt
+            tx.copy_(xn)
+            tr.copy_(rn)
+            rd = rn.double()
+            res.append((float((rd * rd).sum()), float((th.double() * rd).sum())))
+        return res
+
     def sync_compute(self):
         pass
