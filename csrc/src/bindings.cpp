@@ -83,6 +83,18 @@ py::capsule make_dlpack_u8(uintptr_t ptr, int64_t bytes, int dev) {
   });
 }
 
+// The multi-valued reductions return std::array<double, N>, which pybind11
+// would cast to a list: f with the array returned as a tuple of N floats.
+template <size_t N, size_t... I>
+auto tuple_of(const std::array<double, N> &v, std::index_sequence<I...>) {
+  return py::make_tuple(v[I]...);
+}
+template <size_t N, class... Args> auto returns_tuple(std::array<double, N> (*f)(Args...)) {
+  return [f](Args... args) {
+    return tuple_of(f(std::forward<Args>(args)...), std::make_index_sequence<N>{});
+  };
+}
+
 } // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -309,42 +321,16 @@ PYBIND11_MODULE(_C, m) {
             hipMemcpy((void *)e.buffer_ptr(buf), s.data(), s.size(), hipMemcpyHostToDevice));
       });
 
-  // invalid arguments (std::invalid_argument) surface as ValueErrors
-  auto value_errors = [](auto &&call) {
-    try {
-      return call();
-    } catch (const std::invalid_argument &e) {
-      throw py::value_error(e.what());
-    }
-  };
-  m.def(
-      "jacobi_step",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                     const Rect3 &computeRegion, int streamId, int extendVec) {
-        value_errors([&] {
-          jacobi_step(eng, dom, qi, region, computeRegion, streamId, extendVec);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("region"),
-      py::arg("compute_region"), py::arg("stream_id") = 0, py::arg("extend_vec") = 0);
-  m.def(
-      "jacobi_step_kernel",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                     const Rect3 &computeRegion, int extendVec) {
-        return value_errors([&] {
-          return std::string(jacobi_step_kernel(eng, dom, qi, region, computeRegion, extendVec));
-        });
-      },
-      py::arg("engine"), py::arg("dom"), py::arg("qi"), py::arg("region"),
-      py::arg("compute_region"), py::arg("extend_vec") = 0);
-  m.def("fill_f32", [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                                   float value, bool nextBuf) {
-    value_errors([&] {
-      fill_f32(eng, dom, qi, region, value, nextBuf);
-      return 0;
-    });
-  });
+  // The ops below are bound by pointer: pybind11's built-in translator turns
+  // the std::invalid_argument they throw for bad arguments into ValueError and
+  // std::runtime_error into RuntimeError, message kept. A lambda stands only
+  // where a Python value is converted.
+  m.def("jacobi_step", &jacobi_step, py::arg("eng"), py::arg("dom"), py::arg("qi"),
+        py::arg("region"), py::arg("compute_region"), py::arg("stream_id") = 0,
+        py::arg("extend_vec") = 0);
+  m.def("jacobi_step_kernel", &jacobi_step_kernel, py::arg("engine"), py::arg("dom"),
+        py::arg("qi"), py::arg("region"), py::arg("compute_region"), py::arg("extend_vec") = 0);
+  m.def("fill_f32", &fill_f32);
 
   // generic weighted stencil (csrc/src/stencil_op.hip)
   py::class_<StencilTaps>(m, "StencilTaps")
@@ -354,328 +340,95 @@ PYBIND11_MODULE(_C, m) {
   py::enum_<StencilType>(m, "StencilType")
       .value("F32", StencilType::F32)
       .value("F64", StencilType::F64);
-  m.def(
-      "stencil_apply",
-      [](ExchangeEngine &eng, int dom, int64_t srcQ, int64_t dstQ, const Rect3 &region,
-         const StencilTaps &taps, StencilType type, int streamId) {
-        try {
-          stencil_apply(eng, dom, srcQ, dstQ, region, taps, type, streamId);
-        } catch (const std::invalid_argument &e) {
-          throw py::value_error(e.what());
-        }
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("src_q"), py::arg("dst_q"), py::arg("region"),
-      py::arg("taps"), py::arg("type"), py::arg("stream_id") = 0);
+  m.def("stencil_apply", &stencil_apply, py::arg("eng"), py::arg("dom"), py::arg("src_q"),
+        py::arg("dst_q"), py::arg("region"), py::arg("taps"), py::arg("type"),
+        py::arg("stream_id") = 0);
 
-  // vector operations (csrc/src/vector_ops.hip); invalid arguments are ValueErrors
-  m.def(
-      "field_dot",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
-                     const Rect3 &region, int streamId) {
-        return value_errors(
-            [&] { return field_dot(eng, dom, a, aNext, b, bNext, region, streamId); });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
-      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_dot_begin",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_dot_begin(eng, dom, a, aNext, b, bNext, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
-      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_axpby",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
-                     double beta, int64_t y, bool yNext, int64_t out, bool outNext,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_axpby(eng, dom, alpha, x, xNext, beta, y, yNext, out, outNext, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
-      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"), py::arg("out_next"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_axpbypcz",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
-                     double beta, int64_t y, bool yNext, double gamma, int64_t z, bool zNext,
-                     int64_t out, bool outNext, const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_axpbypcz(eng, dom, alpha, x, xNext, beta, y, yNext, gamma, z, zNext, out, outNext,
-                         region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
-      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("gamma"), py::arg("z"),
-      py::arg("z_next"), py::arg("out"), py::arg("out_next"), py::arg("region"),
-      py::arg("stream_id") = 0);
-  m.def(
-      "field_scaled_update",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext, int64_t d,
-                     bool dNext, double beta, int64_t y, bool yNext, double gamma, int64_t z,
-                     bool zNext, int64_t out, bool outNext, const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_scaled_update(eng, dom, alpha, x, xNext, d, dNext, beta, y, yNext, gamma, z,
-                              zNext, out, outNext, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
-      py::arg("d"), py::arg("d_next"), py::arg("beta"), py::arg("y"), py::arg("y_next"),
-      py::arg("gamma"), py::arg("z"), py::arg("z_next"), py::arg("out"), py::arg("out_next"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  // variable-coefficient diffusion operator (csrc/src/diffusion_op.hip)
+  // vector operations (csrc/src/vector_ops.hip). A reduction is bound twice
+  // with one argument list: the blocking form and its *_begin form.
+  auto def_reduction = [&m](const char *name, auto blocking, auto begin, const auto &...args) {
+    m.def(name, blocking, args...);
+    m.def((std::string(name) + "_begin").c_str(), begin, args...);
+  };
+  def_reduction("field_dot", &field_dot, &field_dot_begin, py::arg("eng"), py::arg("dom"),
+                py::arg("a"), py::arg("a_next"), py::arg("b"), py::arg("b_next"),
+                py::arg("region"), py::arg("stream_id") = 0);
+  m.def("field_axpby", &field_axpby, py::arg("eng"), py::arg("dom"), py::arg("alpha"),
+        py::arg("x"), py::arg("x_next"), py::arg("beta"), py::arg("y"), py::arg("y_next"),
+        py::arg("out"), py::arg("out_next"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def("field_axpbypcz", &field_axpbypcz, py::arg("eng"), py::arg("dom"), py::arg("alpha"),
+        py::arg("x"), py::arg("x_next"), py::arg("beta"), py::arg("y"), py::arg("y_next"),
+        py::arg("gamma"), py::arg("z"), py::arg("z_next"), py::arg("out"), py::arg("out_next"),
+        py::arg("region"), py::arg("stream_id") = 0);
+  m.def("field_scaled_update", &field_scaled_update, py::arg("eng"), py::arg("dom"),
+        py::arg("alpha"), py::arg("x"), py::arg("x_next"), py::arg("d"), py::arg("d_next"),
+        py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("gamma"), py::arg("z"),
+        py::arg("z_next"), py::arg("out"), py::arg("out_next"), py::arg("region"),
+        py::arg("stream_id") = 0);
+  // variable-coefficient diffusion operator (csrc/src/diffusion_op.hip); h is
+  // a sequence of three floats in Python, a double[3] in C++
   m.def(
       "diffusion_apply",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t srcQ, int64_t kQ, int64_t dstQ,
-                     const Rect3 &region, const std::array<double, 3> &h, double sigma,
-                     StencilType type, int streamId) {
-        value_errors([&] {
-          diffusion_apply(eng, dom, srcQ, kQ, dstQ, region, h.data(), sigma, type, streamId);
-          return 0;
-        });
+      [](ExchangeEngine &eng, int dom, int64_t srcQ, int64_t kQ, int64_t dstQ, const Rect3 &region,
+         const std::array<double, 3> &h, double sigma, StencilType type, int streamId) {
+        diffusion_apply(eng, dom, srcQ, kQ, dstQ, region, h.data(), sigma, type, streamId);
       },
       py::arg("eng"), py::arg("dom"), py::arg("src_q"), py::arg("k_q"), py::arg("dst_q"),
       py::arg("region"), py::arg("h"), py::arg("sigma"), py::arg("type"),
       py::arg("stream_id") = 0);
   m.def(
       "diffusion_inv_diagonal",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t kQ, int64_t outQ, bool outNext,
-                     const Rect3 &region, const std::array<double, 3> &h, double sigma,
-                     double omega, int streamId) {
-        value_errors([&] {
-          diffusion_inv_diagonal(eng, dom, kQ, outQ, outNext, region, h.data(), sigma, omega,
-                                 streamId);
-          return 0;
-        });
+      [](ExchangeEngine &eng, int dom, int64_t kQ, int64_t outQ, bool outNext, const Rect3 &region,
+         const std::array<double, 3> &h, double sigma, double omega, int streamId) {
+        diffusion_inv_diagonal(eng, dom, kQ, outQ, outNext, region, h.data(), sigma, omega,
+                               streamId);
       },
       py::arg("eng"), py::arg("dom"), py::arg("k_q"), py::arg("out_q"), py::arg("out_next"),
       py::arg("region"), py::arg("h"), py::arg("sigma"), py::arg("omega"),
       py::arg("stream_id") = 0);
   // grid transfer (csrc/src/grid_transfer.hip)
-  m.def(
-      "grid_restrict",
-      [value_errors](ExchangeEngine &fine, int fdom, double alpha, int64_t a, bool aNext,
-                     double beta, int64_t b, bool bNext, ExchangeEngine &coarse, int cdom,
-                     int64_t out, bool outNext, const Rect3 &coarseRegion, int streamId) {
-        value_errors([&] {
-          grid_restrict(fine, fdom, alpha, a, aNext, beta, b, bNext, coarse, cdom, out, outNext,
-                        coarseRegion, streamId);
-          return 0;
-        });
-      },
-      py::arg("fine"), py::arg("fdom"), py::arg("alpha"), py::arg("a"), py::arg("a_next"),
-      py::arg("beta"), py::arg("b"), py::arg("b_next"), py::arg("coarse"), py::arg("cdom"),
-      py::arg("out"), py::arg("out_next"), py::arg("coarse_region"), py::arg("stream_id") = 0);
-  m.def(
-      "grid_prolong_add",
-      [value_errors](ExchangeEngine &coarse, int cdom, int64_t src, bool srcNext,
-                     ExchangeEngine &fine, int fdom, int64_t dst, bool dstNext,
-                     const Rect3 &coarseRegion, int streamId) {
-        value_errors([&] {
-          grid_prolong_add(coarse, cdom, src, srcNext, fine, fdom, dst, dstNext, coarseRegion,
-                           streamId);
-          return 0;
-        });
-      },
-      py::arg("coarse"), py::arg("cdom"), py::arg("src"), py::arg("src_next"), py::arg("fine"),
-      py::arg("fdom"), py::arg("dst"), py::arg("dst_next"), py::arg("coarse_region"),
-      py::arg("stream_id") = 0);
-  m.def(
-      "cg_update",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
-                     const Rect3 &region, int streamId) {
-        return value_errors([&] { return cg_update(eng, dom, alpha, x, p, r, region, streamId); });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "cg_update_begin",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          cg_update_begin(eng, dom, alpha, x, p, r, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "reduction_end",
-      [value_errors](ExchangeEngine &eng, int dom) {
-        return value_errors([&] { return reduction_end(eng, dom); });
-      },
-      py::arg("eng"), py::arg("dom"));
+  m.def("grid_restrict", &grid_restrict, py::arg("fine"), py::arg("fdom"), py::arg("alpha"),
+        py::arg("a"), py::arg("a_next"), py::arg("beta"), py::arg("b"), py::arg("b_next"),
+        py::arg("coarse"), py::arg("cdom"), py::arg("out"), py::arg("out_next"),
+        py::arg("coarse_region"), py::arg("stream_id") = 0);
+  m.def("grid_prolong_add", &grid_prolong_add, py::arg("coarse"), py::arg("cdom"),
+        py::arg("src"), py::arg("src_next"), py::arg("fine"), py::arg("fdom"), py::arg("dst"),
+        py::arg("dst_next"), py::arg("coarse_region"), py::arg("stream_id") = 0);
+  def_reduction("cg_update", &cg_update, &cg_update_begin, py::arg("eng"), py::arg("dom"),
+                py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"), py::arg("region"),
+                py::arg("stream_id") = 0);
+  m.def("reduction_end", &reduction_end, py::arg("eng"), py::arg("dom"));
   // the reductions of singular problems: several values from one pass
-  m.def(
-      "field_sum",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
-                     int streamId) {
-        return value_errors([&] { return field_sum(eng, dom, a, aNext, region, streamId); });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("region"),
-      py::arg("stream_id") = 0);
-  m.def(
-      "field_sum_begin",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, const Rect3 &region,
-                     int streamId) {
-        value_errors([&] {
-          field_sum_begin(eng, dom, a, aNext, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("region"),
-      py::arg("stream_id") = 0);
-  m.def(
-      "field_dot_sums",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
-                     const Rect3 &region, int streamId) {
-        const std::array<double, 3> v = value_errors(
-            [&] { return field_dot_sums(eng, dom, a, aNext, b, bNext, region, streamId); });
-        return py::make_tuple(v[0], v[1], v[2]);
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
-      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_dot_sums_begin",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_dot_sums_begin(eng, dom, a, aNext, b, bNext, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
-      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "cg_update_sum",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
-                     const Rect3 &region, int streamId) {
-        const std::array<double, 2> v = value_errors(
-            [&] { return cg_update_sum(eng, dom, alpha, x, p, r, region, streamId); });
-        return py::make_tuple(v[0], v[1]);
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "cg_update_sum_begin",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, int64_t p, int64_t r,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          cg_update_sum_begin(eng, dom, alpha, x, p, r, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"), py::arg("r"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_axpbyc",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
-                     double beta, int64_t y, bool yNext, double c, int64_t out, bool outNext,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_axpbyc(eng, dom, alpha, x, xNext, beta, y, yNext, c, out, outNext, region,
-                       streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
-      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("c"), py::arg("out"),
-      py::arg("out_next"), py::arg("region"), py::arg("stream_id") = 0);
+  def_reduction("field_sum", &field_sum, &field_sum_begin, py::arg("eng"), py::arg("dom"),
+                py::arg("a"), py::arg("a_next"), py::arg("region"), py::arg("stream_id") = 0);
+  def_reduction("field_dot_sums", returns_tuple(&field_dot_sums), &field_dot_sums_begin,
+                py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+                py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  def_reduction("cg_update_sum", returns_tuple(&cg_update_sum), &cg_update_sum_begin,
+                py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("p"),
+                py::arg("r"), py::arg("region"), py::arg("stream_id") = 0);
+  m.def("field_axpbyc", &field_axpbyc, py::arg("eng"), py::arg("dom"), py::arg("alpha"),
+        py::arg("x"), py::arg("x_next"), py::arg("beta"), py::arg("y"), py::arg("y_next"),
+        py::arg("c"), py::arg("out"), py::arg("out_next"), py::arg("region"),
+        py::arg("stream_id") = 0);
   // the fused passes of BiCGStab
-  m.def(
-      "field_axpby_norm2",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
-                     double beta, int64_t y, bool yNext, int64_t out, bool outNext,
-                     const Rect3 &region, int streamId) {
-        return value_errors([&] {
-          return field_axpby_norm2(eng, dom, alpha, x, xNext, beta, y, yNext, out, outNext, region,
-                                   streamId);
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
-      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"), py::arg("out_next"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_axpby_norm2_begin",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t x, bool xNext,
-                     double beta, int64_t y, bool yNext, int64_t out, bool outNext,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_axpby_norm2_begin(eng, dom, alpha, x, xNext, beta, y, yNext, out, outNext, region,
-                                  streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
-      py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"), py::arg("out_next"),
-      py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_dot_pair",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
-                     const Rect3 &region, int streamId) {
-        const std::array<double, 2> v = value_errors(
-            [&] { return field_dot_pair(eng, dom, a, aNext, b, bNext, region, streamId); });
-        return py::make_tuple(v[0], v[1]);
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
-      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "field_dot_pair_begin",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t a, bool aNext, int64_t b, bool bNext,
-                     const Rect3 &region, int streamId) {
-        value_errors([&] {
-          field_dot_pair_begin(eng, dom, a, aNext, b, bNext, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
-      py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
-  m.def(
-      "bicgstab_update",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t y, bool yNext,
-                     double omega, int64_t z, bool zNext, int64_t x, int64_t r, int64_t t,
-                     bool tNext, int64_t rhat, bool rhatNext, const Rect3 &region, int streamId) {
-        const std::array<double, 2> v = value_errors([&] {
-          return bicgstab_update(eng, dom, alpha, y, yNext, omega, z, zNext, x, r, t, tNext, rhat,
-                                 rhatNext, region, streamId);
-        });
-        return py::make_tuple(v[0], v[1]);
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("y"), py::arg("y_next"),
-      py::arg("omega"), py::arg("z"), py::arg("z_next"), py::arg("x"), py::arg("r"), py::arg("t"),
-      py::arg("t_next"), py::arg("rhat"), py::arg("rhat_next"), py::arg("region"),
-      py::arg("stream_id") = 0);
-  m.def(
-      "bicgstab_update_begin",
-      [value_errors](ExchangeEngine &eng, int dom, double alpha, int64_t y, bool yNext,
-                     double omega, int64_t z, bool zNext, int64_t x, int64_t r, int64_t t,
-                     bool tNext, int64_t rhat, bool rhatNext, const Rect3 &region, int streamId) {
-        value_errors([&] {
-          bicgstab_update_begin(eng, dom, alpha, y, yNext, omega, z, zNext, x, r, t, tNext, rhat,
-                                rhatNext, region, streamId);
-          return 0;
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("y"), py::arg("y_next"),
-      py::arg("omega"), py::arg("z"), py::arg("z_next"), py::arg("x"), py::arg("r"), py::arg("t"),
-      py::arg("t_next"), py::arg("rhat"), py::arg("rhat_next"), py::arg("region"),
-      py::arg("stream_id") = 0);
+  def_reduction("field_axpby_norm2", &field_axpby_norm2, &field_axpby_norm2_begin, py::arg("eng"),
+                py::arg("dom"), py::arg("alpha"), py::arg("x"), py::arg("x_next"),
+                py::arg("beta"), py::arg("y"), py::arg("y_next"), py::arg("out"),
+                py::arg("out_next"), py::arg("region"), py::arg("stream_id") = 0);
+  def_reduction("field_dot_pair", returns_tuple(&field_dot_pair), &field_dot_pair_begin,
+                py::arg("eng"), py::arg("dom"), py::arg("a"), py::arg("a_next"), py::arg("b"),
+                py::arg("b_next"), py::arg("region"), py::arg("stream_id") = 0);
+  def_reduction("bicgstab_update", returns_tuple(&bicgstab_update), &bicgstab_update_begin,
+                py::arg("eng"), py::arg("dom"), py::arg("alpha"), py::arg("y"),
+                py::arg("y_next"), py::arg("omega"), py::arg("z"), py::arg("z_next"),
+                py::arg("x"), py::arg("r"), py::arg("t"), py::arg("t_next"), py::arg("rhat"),
+                py::arg("rhat_next"), py::arg("region"), py::arg("stream_id") = 0);
   m.def(
       "reduction_end_n",
-      [value_errors](ExchangeEngine &eng, int dom, int n) {
+      [](ExchangeEngine &eng, int dom, int n) {
         std::array<double, ExchangeEngine::kReduceValues> v{};
-        value_errors([&] {
-          reduction_end_n(eng, dom, v.data(), n);
-          return 0;
-        });
+        reduction_end_n(eng, dom, v.data(), n);
         py::tuple out(n);
         for (int i = 0; i < n; ++i) out[i] = v[i];
         return out;
@@ -690,15 +443,8 @@ PYBIND11_MODULE(_C, m) {
   py::class_<MhdStepGraph>(m, "MhdStepGraph");
   py::class_<MhdMrStepGraph>(m, "MhdMrStepGraph");
   m.def("step_graphs_alive", &ReplayGraph::alive);
-  m.def(
-      "jacobi_graph_create",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &region,
-                     const Rect3 &computeRegion) {
-        return value_errors(
-            [&] { return jacobi_graph_create(eng, dom, qi, region, computeRegion); });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("region"),
-      py::arg("compute_region"), py::keep_alive<0, 1>());
+  m.def("jacobi_graph_create", &jacobi_graph_create, py::arg("eng"), py::arg("dom"),
+        py::arg("qi"), py::arg("region"), py::arg("compute_region"), py::keep_alive<0, 1>());
   m.def(
       "jacobi_graph_launch", [](JacobiStepGraph &g, int64_t n) { g.launch(n); },
       py::arg("handle"), py::arg("n_steps") = 1);
@@ -733,19 +479,9 @@ PYBIND11_MODULE(_C, m) {
         return out;
       },
       py::arg("x"));
-  m.def(
-      "jacobi_mr_graph_create",
-      [value_errors](ExchangeEngine &eng, int dom, int64_t qi, const Rect3 &interior,
-                     const Rect3 &computeRegion, const std::vector<Rect3> &exteriors,
-                     int extendVec) {
-        return value_errors([&] {
-          return jacobi_mr_graph_create(eng, dom, qi, interior, computeRegion, exteriors,
-                                        extendVec);
-        });
-      },
-      py::arg("eng"), py::arg("dom"), py::arg("qi"), py::arg("interior"),
-      py::arg("compute_region"), py::arg("exteriors"), py::arg("extend_vec") = 2,
-      py::keep_alive<0, 1>());
+  m.def("jacobi_mr_graph_create", &jacobi_mr_graph_create, py::arg("eng"), py::arg("dom"),
+        py::arg("qi"), py::arg("interior"), py::arg("compute_region"), py::arg("exteriors"),
+        py::arg("extend_vec") = 2, py::keep_alive<0, 1>());
   m.def("jacobi_mr_graph_stream", [](JacobiMrStepGraph &g) { return g.stream(); });
   m.def("jacobi_mr_graph_pre", [](JacobiMrStepGraph &g) { g.pre(); });
   m.def("jacobi_mr_graph_post", [](JacobiMrStepGraph &g) { g.post(); });
@@ -877,17 +613,8 @@ PYBIND11_MODULE(_C, m) {
       .def("set_placement_trivial",
            [](DistributedDomain &d) { d.set_placement(PlacementStrategy::Trivial); })
       .def("set_exchange_groups", &DistributedDomain::set_exchange_groups)
-      .def("set_boundary",
-           [](DistributedDomain &d, const std::string &face, Boundary kind, double value,
-              const std::vector<int64_t> &quantities) {
-             try {
-               d.set_boundary(face, kind, value, quantities);
-             } catch (const std::invalid_argument &e) {
-               throw py::value_error(e.what());
-             }
-           },
-           py::arg("face"), py::arg("kind"), py::arg("value") = 0.0,
-           py::arg("quantities") = std::vector<int64_t>{})
+      .def("set_boundary", &DistributedDomain::set_boundary, py::arg("face"), py::arg("kind"),
+           py::arg("value") = 0.0, py::arg("quantities") = std::vector<int64_t>{})
       .def("boundary_bytes", &DistributedDomain::boundary_bytes)
       .def("realize", &DistributedDomain::realize)
       .def("exchange", &DistributedDomain::exchange, py::arg("group") = 0)

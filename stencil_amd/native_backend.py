@@ -704,41 +704,53 @@ class NativeBackend:
 
     # ---- vector operations (csrc/src/vector_ops.hip) ----
     # `boxes` holds one global box (lo, hi) per local domain; an operand is
-    # (quantity index, next_buf). The reductions return one fp64 sum per
-    # local domain: every domain's kernel is launched before the first
-    # wait, so a reduction costs one host sync per domain.
+    # (quantity index, next_buf). The reductions return one fp64 sum (or one
+    # tuple of sums) per local domain: every domain's kernel is launched
+    # before the first wait, so a reduction costs one host sync per domain.
+    def _each_box(self, boxes, stream_id: int, op, *args):
+        """op(engine, li, *args, rect, stream_id), the shape of every _C
+        vector op, on every local domain's box in li order"""
+        for li, (lo, hi) in enumerate(boxes):
+            op(self.engine, li, *args, _rect3(lo, hi), stream_id)
+
+    def _reduce_n(self, boxes, stream_id: int, n_values: int, begin, *args) -> List[tuple]:
+        """begin(engine, li, *args, rect, stream_id), a *_begin op, on every
+        local domain, then reduction_end_n on each begun one (also when a
+        begin raised): one tuple of n_values fp64 sums per local domain"""
+        n = 0
+        try:
+            for li, (lo, hi) in enumerate(boxes):
+                begin(self.engine, li, *args, _rect3(lo, hi), stream_id)
+                n += 1
+        finally:
+            out = [_C.reduction_end_n(self.engine, li, n_values) for li in range(n)]
+        return out
+
+    def _reduce_1(self, boxes, stream_id: int, begin, *args) -> List[float]:
+        return [v[0] for v in self._reduce_n(boxes, stream_id, 1, begin, *args)]
+
     def field_dot(self, boxes, a: int, a_next: bool, b: int, b_next: bool,
                   stream_id: int = 0) -> List[float]:
         """per local domain: sum of a * b over its box, products and sums
         in fp64, deterministic. ValueError (nothing launched) on an unknown
         quantity, a non-float32/float64 or mixed element size, or a box
         outside the allocation."""
-        n = 0
-        try:
-            for li, (lo, hi) in enumerate(boxes):
-                _C.field_dot_begin(self.engine, li, a, a_next, b, b_next, _rect3(lo, hi),
-                                   stream_id)
-                n += 1
-        finally:
-            out = [_C.reduction_end(self.engine, li) for li in range(n)]
-        return out
+        return self._reduce_1(boxes, stream_id, _C.field_dot_begin, a, a_next, b, b_next)
 
     def field_axpby(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
                     y_next: bool, out: int, out_next: bool, stream_id: int = 0):
         """out = alpha * x + beta * y over each local domain's box, in the
         quantity's type; out may alias x or y. Enqueued, not awaited."""
-        for li, (lo, hi) in enumerate(boxes):
-            _C.field_axpby(self.engine, li, alpha, x, x_next, beta, y, y_next, out, out_next,
-                           _rect3(lo, hi), stream_id)
+        self._each_box(boxes, stream_id, _C.field_axpby, alpha, x, x_next, beta, y, y_next, out,
+                       out_next)
 
     def field_axpbypcz(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
                        y_next: bool, gamma: float, z: int, z_next: bool, out: int,
                        out_next: bool, stream_id: int = 0):
         """out = alpha * x + beta * y + gamma * z over each local domain's
         box; out may alias any input. Enqueued, not awaited."""
-        for li, (lo, hi) in enumerate(boxes):
-            _C.field_axpbypcz(self.engine, li, alpha, x, x_next, beta, y, y_next, gamma, z, z_next,
-                              out, out_next, _rect3(lo, hi), stream_id)
+        self._each_box(boxes, stream_id, _C.field_axpbypcz, alpha, x, x_next, beta, y, y_next,
+                       gamma, z, z_next, out, out_next)
 
     def field_scaled_update(self, boxes, alpha: float, x: int, x_next: bool, d: int, d_next: bool,
                             beta: float, y: int, y_next: bool, gamma: float, z: int,
@@ -746,9 +758,8 @@ class NativeBackend:
         """out = alpha * x + d * (beta * y + gamma * z) over each local
         domain's box, d a quantity; out may alias any input. Enqueued, not
         awaited."""
-        for li, (lo, hi) in enumerate(boxes):
-            _C.field_scaled_update(self.engine, li, alpha, x, x_next, d, d_next, beta, y, y_next,
-                                   gamma, z, z_next, out, out_next, _rect3(lo, hi), stream_id)
+        self._each_box(boxes, stream_id, _C.field_scaled_update, alpha, x, x_next, d, d_next, beta,
+                       y, y_next, gamma, z, z_next, out, out_next)
 
     # ---- variable-coefficient diffusion (csrc/src/diffusion_op.hip) ----
     @staticmethod
@@ -805,59 +816,31 @@ class NativeBackend:
                   stream_id: int = 0) -> List[float]:
         """fused CG update per local domain: curr[x] += alpha * curr[p];
         curr[r] -= alpha * next[p]; returns each domain's sum of r_new^2"""
-        n = 0
-        try:
-            for li, (lo, hi) in enumerate(boxes):
-                _C.cg_update_begin(self.engine, li, alpha, x, p, r, _rect3(lo, hi), stream_id)
-                n += 1
-        finally:
-            out = [_C.reduction_end(self.engine, li) for li in range(n)]
-        return out
+        return self._reduce_1(boxes, stream_id, _C.cg_update_begin, alpha, x, p, r)
 
     # ---- the reductions of singular problems: several values per pass ----
-    def _reduce_n(self, boxes, n_values: int, begin) -> List[tuple]:
-        """begin(li, rect) on every local domain, then reduction_end_n on
-        each: one tuple of n_values fp64 sums per local domain"""
-        n = 0
-        try:
-            for li, (lo, hi) in enumerate(boxes):
-                begin(li, _rect3(lo, hi))
-                n += 1
-        finally:
-            out = [_C.reduction_end_n(self.engine, li, n_values) for li in range(n)]
-        return out
-
     def field_sum(self, boxes, a: int, a_next: bool, stream_id: int = 0) -> List[float]:
         """per local domain: sum of a over its box in fp64, deterministic;
         the ValueErrors of field_dot"""
-        return [v[0] for v in self._reduce_n(
-            boxes, 1,
-            lambda li, rect: _C.field_sum_begin(self.engine, li, a, a_next, rect, stream_id))]
+        return self._reduce_1(boxes, stream_id, _C.field_sum_begin, a, a_next)
 
     def field_dot_sums(self, boxes, a: int, a_next: bool, b: int, b_next: bool,
                        stream_id: int = 0) -> List[tuple]:
         """per local domain: (sum a * b, sum a, sum b) over its box from one
         pass, in fp64, deterministic; a and b may be the same buffer"""
-        return self._reduce_n(
-            boxes, 3,
-            lambda li, rect: _C.field_dot_sums_begin(self.engine, li, a, a_next, b, b_next, rect,
-                                                     stream_id))
+        return self._reduce_n(boxes, stream_id, 3, _C.field_dot_sums_begin, a, a_next, b, b_next)
 
     def cg_update_sum(self, boxes, alpha: float, x: int, p: int, r: int,
                       stream_id: int = 0) -> List[tuple]:
         """cg_update per local domain, returning (sum r_new^2, sum r_new)"""
-        return self._reduce_n(
-            boxes, 2,
-            lambda li, rect: _C.cg_update_sum_begin(self.engine, li, alpha, x, p, r, rect,
-                                                    stream_id))
+        return self._reduce_n(boxes, stream_id, 2, _C.cg_update_sum_begin, alpha, x, p, r)
 
     def field_axpbyc(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
                      y_next: bool, c: float, out: int, out_next: bool, stream_id: int = 0):
         """out = alpha * x + beta * y + c over each local domain's box, in
         the quantity's type; out may alias x or y. Enqueued, not awaited."""
-        for li, (lo, hi) in enumerate(boxes):
-            _C.field_axpbyc(self.engine, li, alpha, x, x_next, beta, y, y_next, c, out, out_next,
-                            _rect3(lo, hi), stream_id)
+        self._each_box(boxes, stream_id, _C.field_axpbyc, alpha, x, x_next, beta, y, y_next, c,
+                       out, out_next)
 
     # ---- the fused passes of BiCGStab ----
     def field_axpby_norm2(self, boxes, alpha: float, x: int, x_next: bool, beta: float, y: int,
@@ -865,19 +848,13 @@ class NativeBackend:
                           stream_id: int = 0) -> List[float]:
         """field_axpby per local domain, returning each domain's sum of
         out^2 from the same pass"""
-        return [v[0] for v in self._reduce_n(
-            boxes, 1,
-            lambda li, rect: _C.field_axpby_norm2_begin(self.engine, li, alpha, x, x_next, beta,
-                                                        y, y_next, out, out_next, rect,
-                                                        stream_id))]
+        return self._reduce_1(boxes, stream_id, _C.field_axpby_norm2_begin, alpha, x, x_next,
+                              beta, y, y_next, out, out_next)
 
     def field_dot_pair(self, boxes, a: int, a_next: bool, b: int, b_next: bool,
                        stream_id: int = 0) -> List[tuple]:
         """per local domain: (sum a * b, sum a * a) over its box from one pass"""
-        return self._reduce_n(
-            boxes, 2,
-            lambda li, rect: _C.field_dot_pair_begin(self.engine, li, a, a_next, b, b_next, rect,
-                                                     stream_id))
+        return self._reduce_n(boxes, stream_id, 2, _C.field_dot_pair_begin, a, a_next, b, b_next)
 
     def bicgstab_update(self, boxes, alpha: float, y: int, y_next: bool, omega: float, z: int,
                         z_next: bool, x: int, r: int, t: int, t_next: bool, rhat: int,
@@ -885,11 +862,8 @@ class NativeBackend:
         """fused BiCGStab update per local domain: curr[x] += alpha * y +
         omega * z; curr[r] -= omega * t; returns each domain's
         (sum r_new^2, sum rhat * r_new)"""
-        return self._reduce_n(
-            boxes, 2,
-            lambda li, rect: _C.bicgstab_update_begin(self.engine, li, alpha, y, y_next, omega, z,
-                                                      z_next, x, r, t, t_next, rhat, rhat_next,
-                                                      rect, stream_id))
+        return self._reduce_n(boxes, stream_id, 2, _C.bicgstab_update_begin, alpha, y, y_next,
+                              omega, z, z_next, x, r, t, t_next, rhat, rhat_next)
 
     def jacobi_graph_create(self, li: int, qi: int, region_lo: Vec, region_hi: Vec,
                             c_lo: Vec, c_hi: Vec) -> "_C.JacobiStepGraph":

@@ -64,39 +64,5 @@ from .._C import (  # noqa: F401
     stencil_apply,
 )
 
-__all__ = [
-    "FieldStats",
-    "MhdCoeffs",
-    "StencilTaps",
-    "StencilType",
-    "bicgstab_update",
-    "bicgstab_update_begin",
-    "cg_update",
-    "cg_update_begin",
-    "cg_update_sum",
-    "cg_update_sum_begin",
-    "diffusion_apply",
-    "diffusion_inv_diagonal",
-    "field_axpby",
-    "field_axpby_norm2",
-    "field_axpby_norm2_begin",
-    "field_axpbyc",
-    "field_dot",
-    "field_dot_begin",
-    "field_dot_pair",
-    "field_dot_pair_begin",
-    "field_dot_sums",
-    "field_dot_sums_begin",
-    "field_scaled_update",
-    "field_stats",
-    "field_sum",
-    "field_sum_begin",
-    "fill_f32",
-    "init_harmonic_f64",
-    "jacobi_step",
-    "mhd_div_pass",
-    "mhd_substep",
-    "reduction_end",
-    "reduction_end_n",
-    "stencil_apply",
-]
+# exactly the names imported above (nothing else here is public)
+__all__ = [name for name in dir() if not name.startswith("_")]

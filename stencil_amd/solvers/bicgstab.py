@@ -64,52 +64,28 @@ import math
 import time
 from typing import Optional
 
-import numpy as np
-
 from ..boundary import Boundary
 from ..core import DataHandle, DistributedDomain, Next
 from ..stencil import Stencil
-from .cg import _FACES, CGResult
+from ._common import (  # noqa: F401  (check_radius is re-exported)
+    CGResult,
+    check_faces,
+    check_quantities,
+    check_radius,
+    operator_apply,
+    overlapped_apply,
+)
 
 MAX_RESTARTS = 10
-
-
-def check_radius(who: str, dd: DistributedDomain, operator: Stencil):
-    """ValueError unless dd's radius covers the stencil in every direction"""
-    need = operator.radius()
-    for dz in (-1, 0, 1):
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                if (dx, dy, dz) != (0, 0, 0) and dd.radius.dir(dx, dy, dz) < need.dir(dx, dy, dz):
-                    raise ValueError(
-                        f"{who}: the domain's radius {dd.radius.dir(dx, dy, dz)} in "
-                        f"direction {(dx, dy, dz)} does not cover the stencil's "
-                        f"{need.dir(dx, dy, dz)}"
-                    )
 
 
 def check_homogeneous_boundary(who: str, dd: DistributedDomain, handles):
     """ValueError unless every non-periodic face of the given quantities is
     FIXED(0), MIRROR, ANTIMIRROR or CLAMP"""
-    spec = dd.boundary
-    if spec is None:
-        return
-    for h in handles:
-        for a in range(3):
-            if spec.periodic[a]:
-                continue
-            for s in (0, 1):
-                k = spec.kind(h.index, a, s)
-                ok = k in (Boundary.MIRROR, Boundary.ANTIMIRROR, Boundary.CLAMP) or (
-                    k == Boundary.FIXED and float(spec.value(h.index, a, s)) == 0.0
-                )
-                if not ok:
-                    raise ValueError(
-                        f"{who}: boundary {k.name} on face {_FACES[2 * a + s]} "
-                        f"of quantity {h.name or h.index}: the operator must be linear and "
-                        "homogeneous (PERIODIC, FIXED(0), MIRROR, ANTIMIRROR or CLAMP); "
-                        "fold inhomogeneous boundary data into b"
-                    )
+    check_faces(f"{who}: ", dd, handles,
+                (Boundary.FIXED, Boundary.MIRROR, Boundary.ANTIMIRROR, Boundary.CLAMP),
+                ": the operator must be linear and homogeneous (PERIODIC, FIXED(0), MIRROR, "
+                "ANTIMIRROR or CLAMP); fold inhomogeneous boundary data into b")
 
 
 def _usable(v: float) -> bool:
@@ -140,42 +116,22 @@ class BiCGStab:
         CLAMP, a preconditioner without apply or without y and z, and y or
         z without a preconditioner."""
         who = "BiCGStab"
-        if not dd._realized:
-            raise ValueError(f"{who}: construct after dd.realize()")
         if not isinstance(operator, Stencil):
             raise ValueError(f"{who}: the operator is a Stencil (a DiffusionOperator is not "
                              "supported)")
-        hs = (x, b, r, rhat, p)
-        if any(not isinstance(h, DataHandle) for h in hs):
-            raise TypeError(f"{who}: x, b, r, rhat and p are DataHandles")
-        if len({h.index for h in hs}) != 5:
-            raise ValueError(f"{who}: x, b, r, rhat and p must be five distinct quantities")
-        if preconditioner is not None:
-            if not callable(getattr(preconditioner, "apply", None)):
-                raise ValueError(f"{who}: the preconditioner has no apply(r, z)")
-            if (not isinstance(y, DataHandle) or not isinstance(z, DataHandle)
-                    or len({h.index for h in hs + (y, z)}) != 7):
-                raise ValueError(f"{who}: a preconditioner needs y and z, two more distinct "
-                                 "quantities")
-            hs = hs + (y, z)
-        elif y is not None or z is not None:
-            raise ValueError(f"{who}: y or z is given but no preconditioner")
-        dt = x.dtype
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError(f"{who} supports float32/float64 quantities, got {dt}")
-        if any(h.dtype != dt for h in hs):
-            raise ValueError(f"{who}: the quantities must share one dtype, got "
-                             + ", ".join(str(h.dtype) for h in hs))
-        check_radius(who, dd, operator)
+        if preconditioner is not None and not callable(getattr(preconditioner, "apply", None)):
+            raise ValueError(f"{who}: the preconditioner has no apply(r, z)")
         phat, shat = (p, r) if preconditioner is None else (y, z)
-        groups = dd.exchange_groups or [list(range(len(dd._data)))]
-        for h, g, what in ((phat, group_p, "group_p"), (shat, group_r, "group_r"),
-                           (x, group_x, "group_x")):
-            if g is None and what == "group_x":
-                continue
-            if not (isinstance(g, int) and 0 <= g < len(groups) and h.index in groups[g]):
-                raise ValueError(f"{who}: {h.name or h.index} is not in exchange group "
-                                 f"{what}={g}")
+        check_quantities(
+            who, dd, (("x", x), ("b", b), ("r", r), ("rhat", rhat), ("p", p)),
+            optional=((preconditioner is not None, (y, z),
+                       "a preconditioner needs y and z, two more distinct quantities",
+                       "y or z is given but no preconditioner"),),
+            groups=[(h, g, f"{{name}} is not in exchange group {what}={g}")
+                    for h, g, what in ((phat, group_p, "group_p"), (shat, group_r, "group_r"),
+                                       (x, group_x, "group_x"))
+                    if not (g is None and what == "group_x")])
+        check_radius(who, dd, operator)
         checked = {h.index: h for h in (x, p, phat, shat)}
         check_homogeneous_boundary(who, dd, checked.values())
         self.dd, self.A = dd, operator
@@ -197,13 +153,7 @@ class BiCGStab:
         """next[h] = A curr[h] on every local domain, halos refreshed"""
         dd = self.dd
         dd.backend.sync_compute()  # the exchange reads h on other streams
-        if overlap:
-            dd.apply_stencil(self.A, h, where="interior")
-            dd.exchange(group)
-            dd.apply_stencil(self.A, h, where="exterior")
-        else:
-            dd.exchange(group)
-            dd.apply_stencil(self.A, h, where="all")
+        overlapped_apply(dd, lambda where: operator_apply(dd, self.A, h, where), group, overlap)
         dd.backend.sync_compute()
 
     def _precondition(self, f: DataHandle, e: DataHandle):

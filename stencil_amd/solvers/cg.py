@@ -83,28 +83,21 @@ from __future__ import annotations
 
 import math
 import time
-from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Optional
 
 import numpy as np
 
 from ..boundary import Boundary
 from ..core import DataHandle, DistributedDomain, Next
 from ..stencil import Stencil
-
-
-@dataclass
-class CGResult:
-    converged: bool
-    iterations: int
-    # relative recursive residual norm sqrt(r.r / b.b) after each iteration;
-    # entry 0 is the initial one (1.0 when x0 = 0)
-    residuals: List[float] = field(default_factory=list)
-    # "converged" | "max_iter" | "breakdown" | "zero_rhs" | "stagnated"
-    reason: str = ""
-
-
-_FACES = ("x-", "x+", "y-", "y+", "z-", "z+")
+from ._common import (  # noqa: F401  (CGResult and check_radius are re-exported)
+    CGResult,
+    check_faces,
+    check_quantities,
+    check_radius,
+    operator_apply,
+    overlapped_apply,
+)
 
 
 def check_operator(who: str, dd: DistributedDomain, operator):
@@ -119,60 +112,23 @@ def check_operator(who: str, dd: DistributedDomain, operator):
             raise ValueError(f"{who}: the DiffusionOperator belongs to another domain")
     if not operator.is_symmetric():
         raise ValueError(f"{who}: the stencil is not symmetric (w(o) != w(-o))")
-    need = operator.radius()
-    for dz in (-1, 0, 1):
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                if (dx, dy, dz) != (0, 0, 0) and dd.radius.dir(dx, dy, dz) < need.dir(dx, dy, dz):
-                    raise ValueError(
-                        f"{who}: the domain's radius {dd.radius.dir(dx, dy, dz)} in "
-                        f"direction {(dx, dy, dz)} does not cover the stencil's "
-                        f"{need.dir(dx, dy, dz)}"
-                    )
+    check_radius(who, dd, operator)
 
 
 def check_boundary(who: str, dd: DistributedDomain, handles):
     """ValueError unless every non-periodic face of the given quantities is
     FIXED(0), MIRROR or ANTIMIRROR"""
-    spec = dd.boundary
-    if spec is None:
-        return
-    for h in handles:
-        for a in range(3):
-            if spec.periodic[a]:
-                continue
-            for s in (0, 1):
-                k = spec.kind(h.index, a, s)
-                ok = k in (Boundary.MIRROR, Boundary.ANTIMIRROR) or (
-                    k == Boundary.FIXED and float(spec.value(h.index, a, s)) == 0.0
-                )
-                if not ok:
-                    raise ValueError(
-                        f"{who}: boundary {k.name} on face {_FACES[2 * a + s]} "
-                        f"of quantity {h.name or h.index}: the operator must be symmetric, "
-                        "linear and homogeneous (PERIODIC, FIXED(0), MIRROR or ANTIMIRROR); "
-                        "fold inhomogeneous boundary data into b"
-                    )
+    check_faces(f"{who}: ", dd, handles, (Boundary.FIXED, Boundary.MIRROR, Boundary.ANTIMIRROR),
+                ": the operator must be symmetric, linear and homogeneous (PERIODIC, FIXED(0), "
+                "MIRROR or ANTIMIRROR); fold inhomogeneous boundary data into b")
 
 
 def check_constant_nullspace(who: str, dd: DistributedDomain, operator, handles):
     """ValueError unless the constant is in the null space of A: every face
     of the given quantities PERIODIC or MIRROR, and an operator without a
     zeroth-order term"""
-    spec = dd.boundary
-    if spec is not None:
-        for h in handles:
-            for a in range(3):
-                if spec.periodic[a]:
-                    continue
-                for s in (0, 1):
-                    k = spec.kind(h.index, a, s)
-                    if k != Boundary.MIRROR:
-                        raise ValueError(
-                            f"{who}: nullspace='constant' but boundary {k.name} on face "
-                            f"{_FACES[2 * a + s]} of quantity {h.name or h.index} pins the "
-                            "constant: A is not singular (every face must be PERIODIC or MIRROR)"
-                        )
+    check_faces(f"{who}: nullspace='constant' but ", dd, handles, (Boundary.MIRROR,),
+                " pins the constant: A is not singular (every face must be PERIODIC or MIRROR)")
     if isinstance(operator, Stencil):
         total = math.fsum(operator.weights)
         scale = math.fsum(abs(w) for w in operator.weights)
@@ -221,47 +177,28 @@ class ConjugateGradient:
         if nullspace not in (None, "constant"):
             raise ValueError(
                 f"ConjugateGradient: nullspace is None or 'constant', got {nullspace!r}")
-        if not dd._realized:
-            raise ValueError("ConjugateGradient: construct after dd.realize()")
-        hs = (x, b, r, p)
-        if len({h.index for h in hs}) != 4:
-            raise ValueError("ConjugateGradient: x, b, r and p must be four distinct quantities")
-        if preconditioner is not None:
-            if not callable(getattr(preconditioner, "apply", None)):
-                raise ValueError("ConjugateGradient: the preconditioner has no apply(r, z)")
-            if not isinstance(z, DataHandle) or z.index in {h.index for h in hs}:
-                raise ValueError(
-                    "ConjugateGradient: a preconditioner needs z, a fifth distinct quantity")
-            hs = hs + (z,)
-        elif z is not None:
-            raise ValueError("ConjugateGradient: z is given but no preconditioner")
-        if correction is not None:
-            if not isinstance(correction, DataHandle) or correction.index in {h.index for h in hs}:
-                raise ValueError("ConjugateGradient: correction must be one more distinct quantity")
-            if group_x is None:
-                raise ValueError("ConjugateGradient: correction needs group_x, the exchange "
-                                 "group of x")
-            hs = hs + (correction,)
-        dt = x.dtype
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError(f"ConjugateGradient supports float32/float64 quantities, got {dt}")
-        if any(h.dtype != dt for h in hs):
-            raise ValueError(
-                "ConjugateGradient: the quantities must share one dtype, got "
-                + ", ".join(str(h.dtype) for h in hs)
-            )
-        check_operator("ConjugateGradient", dd, operator)
-        if not isinstance(operator, Stencil) and operator.k.dtype != dt:
-            raise ValueError(
-                f"ConjugateGradient: the coefficient is {operator.k.dtype}, the unknown {dt}")
-        groups = dd.exchange_groups or [list(range(len(dd._data)))]
-        if not (0 <= group_p < len(groups) and p.index in groups[group_p]):
-            raise ValueError(f"ConjugateGradient: p is not in exchange group {group_p}")
-        if group_x is not None and not (0 <= group_x < len(groups) and x.index in groups[group_x]):
-            raise ValueError(f"ConjugateGradient: x is not in exchange group {group_x}")
-        check_boundary("ConjugateGradient", dd, (p, x))
+        who = "ConjugateGradient"
+        if preconditioner is not None and not callable(getattr(preconditioner, "apply", None)):
+            raise ValueError(f"{who}: the preconditioner has no apply(r, z)")
+        if correction is not None and group_x is None:
+            raise ValueError(f"{who}: correction needs group_x, the exchange group of x")
+        groups = [(p, group_p, f"p is not in exchange group {group_p}")]
+        if group_x is not None:
+            groups.append((x, group_x, f"x is not in exchange group {group_x}"))
+        check_quantities(
+            who, dd, (("x", x), ("b", b), ("r", r), ("p", p)),
+            optional=((preconditioner is not None, (z,),
+                       "a preconditioner needs z, a fifth distinct quantity",
+                       "z is given but no preconditioner"),
+                      (correction is not None, (correction,),
+                       "correction must be one more distinct quantity", None)),
+            groups=groups)
+        check_operator(who, dd, operator)
+        if not isinstance(operator, Stencil) and operator.k.dtype != x.dtype:
+            raise ValueError(f"{who}: the coefficient is {operator.k.dtype}, the unknown {x.dtype}")
+        check_boundary(who, dd, (p, x))
         if nullspace is not None:
-            check_constant_nullspace("ConjugateGradient", dd, operator, (p, x))
+            check_constant_nullspace(who, dd, operator, (p, x))
         self.nullspace = nullspace
         self._cells = float(dd.size[0]) * float(dd.size[1]) * float(dd.size[2])  # N
         self._bb = 0.0  # ||P b||^2 of the last nullspace solve, for _refine
@@ -280,19 +217,7 @@ class ConjugateGradient:
     def _apply(self, h: DataHandle, group: int, overlap: bool):
         """next[h] = A curr[h] on every local domain, halos refreshed"""
         dd = self.dd
-        if isinstance(self.A, Stencil):
-            def op(where):
-                dd.apply_stencil(self.A, h, where=where)
-        else:  # a DiffusionOperator
-            def op(where):
-                self.A.apply(h, where=where)
-        if overlap:
-            op("interior")
-            dd.exchange(group)
-            op("exterior")
-        else:
-            dd.exchange(group)
-            op("all")
+        overlapped_apply(dd, lambda where: operator_apply(dd, self.A, h, where), group, overlap)
         dd.backend.sync_compute()
 
     def solve(self, tol: float = 1e-6, max_iter: int = 1000, x0_zero: bool = True,

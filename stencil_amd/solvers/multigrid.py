@@ -62,6 +62,7 @@ import numpy as np
 from ..boundary import FACES, Boundary
 from ..core import DataHandle, DistributedDomain, Next
 from ..stencil import Stencil
+from ._common import operator_apply, overlapped_apply
 from .cg import check_boundary, check_operator
 from .diffusion import DiffusionOperator
 from .transfer import GridTransfer
@@ -77,10 +78,7 @@ class _Level:
         self.transfer: Optional[GridTransfer] = None  # to the next coarser level
 
     def apply(self, where):
-        if self.w is None:
-            self.A.apply(self.e, where=where)
-        else:
-            self.dd.apply_stencil(self.A, self.e, where=where)
+        operator_apply(self.dd, self.A, self.e, where)
 
 
 def _centre(who: str, A: Stencil) -> float:
@@ -277,14 +275,9 @@ class GeometricMultigrid:
         """next[e] = A e, halos refreshed; enqueued, stream 0 may go on"""
         dd = lv.dd
         dd.backend.sync_compute()  # the exchange reads e on other streams
+        overlapped_apply(dd, lv.apply, lv.group, overlap)
         if overlap:
-            lv.apply("interior")
-            dd.exchange(lv.group)
-            lv.apply("exterior")
             dd.backend.sync_compute()  # the exterior slabs ran on stream 1
-        else:
-            dd.exchange(lv.group)
-            lv.apply("all")
 
     def _sweep(self, lv: _Level, f: DataHandle, overlap: bool):
         self._operator(lv, overlap)

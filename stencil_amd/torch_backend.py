@@ -369,6 +369,15 @@ class TorchBackend:
             raise ValueError(f"{op}: region {lo}..{hi} is outside the allocation")
         return [dom.region(qi, pos, ext, nxt) for qi, nxt in operands]
 
+    def _box_views(self, op, boxes, operands, scalars=()):
+        """for every non-empty box in turn: the operands' views, then the
+        scalars rounded to the views' dtype (0-d tensors on their device)"""
+        for li, (lo, hi) in enumerate(boxes):
+            v = self._vector_views(op, li, lo, hi, operands)
+            if v is not None:
+                yield (*v, *(torch.tensor(s, dtype=v[0].dtype, device=v[0].device)
+                             for s in scalars))
+
     def field_dot(self, boxes, a, a_next, b, b_next, stream_id=0):
         """per local domain: sum of a * b over its box, products and sums in fp64"""
         out = []
@@ -380,43 +389,27 @@ class TorchBackend:
     def field_axpby(self, boxes, alpha, x, x_next, beta, y, y_next, out, out_next, stream_id=0):
         """out = alpha * x + beta * y in the quantity's type, alpha and beta
         rounded to it once; two products and one sum, no FMA"""
-        for li, (lo, hi) in enumerate(boxes):
-            v = self._vector_views("field_axpby", li, lo, hi,
-                                   [(x, x_next), (y, y_next), (out, out_next)])
-            if v is None:
-                continue
-            tx, ty, tout = v
-            al = torch.tensor(alpha, dtype=tx.dtype, device=tx.device)
-            be = torch.tensor(beta, dtype=tx.dtype, device=tx.device)
+        for tx, ty, tout, al, be in self._box_views(
+                "field_axpby", boxes, [(x, x_next), (y, y_next), (out, out_next)], (alpha, beta)):
             tout.copy_(al * tx + be * ty)
 
     def field_axpbypcz(self, boxes, alpha, x, x_next, beta, y, y_next, gamma, z, z_next, out,
                        out_next, stream_id=0):
         """out = alpha * x + beta * y + gamma * z in the quantity's type, the
         coefficients rounded to it once; summed left to right, no FMA"""
-        for li, (lo, hi) in enumerate(boxes):
-            v = self._vector_views("field_axpbypcz", li, lo, hi,
-                                   [(x, x_next), (y, y_next), (z, z_next), (out, out_next)])
-            if v is None:
-                continue
-            tx, ty, tz, tout = v
-            al, be, ga = (torch.tensor(c, dtype=tx.dtype, device=tx.device)
-                          for c in (alpha, beta, gamma))
+        for tx, ty, tz, tout, al, be, ga in self._box_views(
+                "field_axpbypcz", boxes, [(x, x_next), (y, y_next), (z, z_next), (out, out_next)],
+                (alpha, beta, gamma)):
             tout.copy_(al * tx + be * ty + ga * tz)
 
     def field_scaled_update(self, boxes, alpha, x, x_next, d, d_next, beta, y, y_next, gamma, z,
                             z_next, out, out_next, stream_id=0):
         """out = alpha * x + d * (beta * y + gamma * z) in the quantity's
         type, the coefficients rounded to it once; no FMA"""
-        for li, (lo, hi) in enumerate(boxes):
-            v = self._vector_views("field_scaled_update", li, lo, hi,
-                                   [(x, x_next), (d, d_next), (y, y_next), (z, z_next),
-                                    (out, out_next)])
-            if v is None:
-                continue
-            tx, td, ty, tz, tout = v
-            al, be, ga = (torch.tensor(c, dtype=tx.dtype, device=tx.device)
-                          for c in (alpha, beta, gamma))
+        for tx, td, ty, tz, tout, al, be, ga in self._box_views(
+                "field_scaled_update", boxes,
+                [(x, x_next), (d, d_next), (y, y_next), (z, z_next), (out, out_next)],
+                (alpha, beta, gamma)):
             tout.copy_(al * tx + td * (be * ty + ga * tz))
 
     # ---- variable-coefficient diffusion: slicing references of
@@ -567,14 +560,18 @@ class TorchBackend:
         tdst += tsrc[:, None, :, None, :, None].expand(ez, 2, ey, 2, ex, 2).reshape(
             2 * ez, 2 * ey, 2 * ex)
 
+    def _check_cg_update(self, op, boxes, x, p, r):
+        """ValueError unless x, p and r are distinct and every operand is
+        valid on every box: nothing has been written then"""
+        if x == p or x == r or p == r:
+            raise ValueError(f"{op}: x, p and r must be distinct quantities")
+        for li, (lo, hi) in enumerate(boxes):
+            self._vector_views(op, li, lo, hi, [(x, False), (p, False), (p, True), (r, False)])
+
     def cg_update(self, boxes, alpha, x, p, r, stream_id=0):
         """the unfused composition: x = 1 x + alpha p; r = 1 r + (-alpha) A p
         (A p in next[p]); returns each domain's dot(r, r)"""
-        if x == p or x == r or p == r:
-            raise ValueError("cg_update: x, p and r must be distinct quantities")
-        for li, (lo, hi) in enumerate(boxes):  # validate every operand before any write
-            self._vector_views("cg_update", li, lo, hi,
-                               [(x, False), (p, False), (p, True), (r, False)])
+        self._check_cg_update("cg_update", boxes, x, p, r)
         self.field_axpby(boxes, 1.0, x, False, alpha, p, False, x, False)
         self.field_axpby(boxes, 1.0, r, False, -alpha, p, True, r, False)
         return self.field_dot(boxes, r, False, r, False)
@@ -603,11 +600,7 @@ class TorchBackend:
 
     def cg_update_sum(self, boxes, alpha, x, p, r, stream_id=0):
         """cg_update, returning (dot(r, r), sum r) per domain"""
-        if x == p or x == r or p == r:
-            raise ValueError("cg_update_sum: x, p and r must be distinct quantities")
-        for li, (lo, hi) in enumerate(boxes):  # validate every operand before any write
-            self._vector_views("cg_update_sum", li, lo, hi,
-                               [(x, False), (p, False), (p, True), (r, False)])
+        self._check_cg_update("cg_update_sum", boxes, x, p, r)
         self.field_axpby(boxes, 1.0, x, False, alpha, p, False, x, False)
         self.field_axpby(boxes, 1.0, r, False, -alpha, p, True, r, False)
         return [(rr, sr) for rr, sr, _ in self.field_dot_sums(boxes, r, False, r, False)]
@@ -616,14 +609,9 @@ class TorchBackend:
                      stream_id=0):
         """out = alpha * x + beta * y + c in the quantity's type, alpha, beta
         and c rounded to it once; summed left to right, no FMA"""
-        for li, (lo, hi) in enumerate(boxes):
-            v = self._vector_views("field_axpbyc", li, lo, hi,
-                                   [(x, x_next), (y, y_next), (out, out_next)])
-            if v is None:
-                continue
-            tx, ty, tout = v
-            al, be, cc = (torch.tensor(s, dtype=tx.dtype, device=tx.device)
-                          for s in (alpha, beta, c))
+        for tx, ty, tout, al, be, cc in self._box_views(
+                "field_axpbyc", boxes, [(x, x_next), (y, y_next), (out, out_next)],
+                (alpha, beta, c)):
             tout.copy_(al * tx + be * ty + cc)
 
     # ---- the fused passes of BiCGStab (vector_ops.hip's third family) ----
